@@ -1,5 +1,5 @@
 # Convenience targets (PYTORCH_ROCM_ARCH=gfx950 is set by setup.py)
-.PHONY: build test test-gpu bench smoke clean
+.PHONY: build test test-gpu bench bench-full smoke clean
 
 build:
 	python setup.py build_ext --inplace
@@ -12,6 +12,9 @@ test-gpu:
 
 bench:
 	python bench.py --steps 30 --warmup 8
+
+bench-full:
+	python bench.py --steps 30 --warmup 8 --full
 
 smoke:
 	python -c "import __graft_entry__ as g; g.build(); g.smoke()"

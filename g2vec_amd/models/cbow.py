@@ -414,8 +414,11 @@ class CbowTrainer:
         replay + verify a tiny all-reduce; G2VEC_DIST_GRAPH=0 opts out).
         A rank that falls back to eager stays collective-compatible with
         ranks that replay graphs — both issue the identical collective
-        sequence per epoch."""
-        if (self.cfg.use_hipgraph and st.graph is None and
+        sequence per epoch. A CPU-device trainer never captures, also on
+        a host that has a GPU: its body would run once during capture,
+        record nothing, and every replay would then be a no-op epoch."""
+        if (self.device.type == "cuda" and
+                self.cfg.use_hipgraph and st.graph is None and
                 not st.graph_failed and st.epoch_idx >= 1 and
                 self.ctx.graph_capture_ok()):
             try:
