@@ -229,8 +229,11 @@ class CbowTrainer:
         if use_general and cfg.dtype != "fp32":
             st.W16 = (W.bfloat16() if cfg.dtype == "bf16" else W.half())
         # gene-sorted instance plan: drives the deterministic backward on
-        # both trainer paths (genes never change across epochs)
-        st.plan = ops.build_scatter_plan(tr.genes, tr.offsets, self.G)
+        # both trainer paths (genes never change across epochs). The
+        # general path's row backward writes one dW row per segment, so it
+        # takes the single-pass layout at every path count.
+        st.plan = ops.build_scatter_plan(tr.genes, tr.offsets, self.G,
+                                         slabs=not use_general)
         if self.n_tr_global + self.n_vl_global == 0:
             raise ValueError(
                 "no paths to train on: the integrated path set is empty "

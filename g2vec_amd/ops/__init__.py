@@ -107,17 +107,19 @@ SLAB_BYTES = 3 << 20     # dO slice per launch; < the 4 MB per-XCD L2
 
 
 def build_scatter_plan(genes: torch.Tensor, offsets: torch.Tensor,
-                       n_genes: int, _force_slabs: bool = False
-                       ) -> ScatterPlan:
+                       n_genes: int, _force_slabs: bool = False,
+                       slabs: bool = True) -> ScatterPlan:
     # _force_slabs: CPU tests exercise the slab geometry (the CPU compute
     # path itself never consumes a slabbed plan)
+    # slabs=False: always one gene-sorted pass — what cbow_bwd_rows needs
+    # (it WRITES one dW row per segment, so a gene may own only one)
     counts = (offsets[1:] - offsets[:-1]).long()
     P = len(counts)
     path_of = torch.repeat_interleave(
         torch.arange(P, device=genes.device), counts)
     slab_paths = SLAB_BYTES // 4
     n_slabs = ((P + slab_paths - 1) // slab_paths
-               if (genes.is_cuda or _force_slabs) else 1)
+               if slabs and (genes.is_cuda or _force_slabs) else 1)
     if n_slabs <= 1:
         sorted_key, perm = torch.sort(genes.long(), stable=True)
     else:
@@ -246,7 +248,13 @@ def cbow_bwd_rows(who, genes, offsets, dO, n_genes: int,
     (the forward's pre-activation H)."""
     if dO.is_cuda:
         if plan is None:
-            plan = build_scatter_plan(genes, offsets, n_genes)
+            plan = build_scatter_plan(genes, offsets, n_genes, slabs=False)
+        if plan.slab_seg_ptr is not None:
+            # a slab-blocked plan has one segment per (slab, gene): the
+            # kernel would overwrite a gene's row once per slab
+            raise RuntimeError(
+                "cbow_bwd_rows needs a single-pass plan "
+                "(build_scatter_plan(..., slabs=False)), got a slab-blocked one")
         return native().cbow_bwd_rows(who, plan.inst_path, plan.seg_start,
                                       plan.seg_gene, dO, int(n_genes),
                                       Hpre=H_pre)

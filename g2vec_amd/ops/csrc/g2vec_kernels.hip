@@ -111,6 +111,11 @@ __device__ __forceinline__ float to_f32(const float f) { return f; }
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
   union { float f; uint32_t u; } x;
   x.f = f;
+  // NaN passes through as a quiet NaN of the same sign: the rounding add
+  // below would carry a large payload out of the exponent (0x7FFFFFFF ->
+  // 0x8000 = -0.0) or round a small one down to inf (0x7F800001 -> 0x7F80)
+  if ((x.u & 0x7FFFFFFFu) > 0x7F800000u)
+    return (uint16_t)((x.u >> 16) | 0x0040u);
   // round-to-nearest-even like torch's .bfloat16()
   uint32_t lsb = (x.u >> 16) & 1u;
   x.u += 0x7FFFu + lsb;
@@ -788,7 +793,7 @@ pcc_edges_kernel(const float* __restrict__ zt, const int* __restrict__ edges,
 // C = Zt Zt^T / S on v_mfma_f32_16x16x4_f32 (exact f32 at the FP32 matrix
 // rate — no xf32 on gfx950, see cdna_hip_programming.md §3). 64x64 tile per
 // 4-wave block (each wave one 32x32 sub-tile = 2x2 16x16 fragments), both
-// operand tiles staged once in LDS (K = S <= 288 fits the 160 KiB budget).
+// operand tiles staged once in LDS (K = S <= 320 fits the 160 KiB budget).
 typedef float f32x4c __attribute__((ext_vector_type(4)));
 
 extern "C" __global__ void __launch_bounds__(256)
