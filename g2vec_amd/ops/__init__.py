@@ -176,15 +176,21 @@ def tf1_lr_t(lr: float, b1: float, b2: float, t: int) -> float:
     return lr * (1.0 - b2 ** t) ** 0.5 / (1.0 - b1 ** t)
 
 
+def _lrt_buf(lrt_buf, W, t: int, lr: float, b1: float, b2: float):
+    """The caller's lr_t device slot, or a fresh one holding this step's."""
+    if lrt_buf is not None:
+        return lrt_buf
+    return torch.tensor([tf1_lr_t(lr, b1, b2, t)], dtype=torch.float32,
+                        device=W.device)
+
+
 def adam_rank1(W, m, v, c, who, t: int, lr: float, b1: float, b2: float,
                eps: float, lrt_buf: Optional[torch.Tensor] = None) -> None:
     """lrt_buf: optional persistent f32[1] device buffer holding lr_t —
     required under hipGraph capture (the per-step value must be read from
     device memory, not baked into the recorded launch)."""
     if W.is_cuda:
-        if lrt_buf is None:
-            lrt_buf = torch.tensor([tf1_lr_t(lr, b1, b2, t)],
-                                   dtype=torch.float32, device=W.device)
+        lrt_buf = _lrt_buf(lrt_buf, W, t, lr, b1, b2)
         native().adam_rank1(W, m, v, c, who, lrt_buf, float(b1), float(b2),
                             float(eps))
         return
@@ -200,9 +206,7 @@ def adam_rank1_fused(W, m, v, c, who, mO, vO, t: int, lr: float,
     adam_rank1 + adam_dense: three launches and an extra full W read).
     Deterministic (fixed per-thread/block fold order)."""
     if W.is_cuda:
-        if lrt_buf is None:
-            lrt_buf = torch.tensor([tf1_lr_t(lr, b1, b2, t)],
-                                   dtype=torch.float32, device=W.device)
+        lrt_buf = _lrt_buf(lrt_buf, W, t, lr, b1, b2)
         native().adam_rank1(W, m, v, c, who, lrt_buf, float(b1), float(b2),
                             float(eps), mO=mO, vO=vO)
         return
@@ -214,9 +218,7 @@ def adam_rank1_fused(W, m, v, c, who, mO, vO, t: int, lr: float,
 def adam_dense(W, m, v, grad, t: int, lr: float, b1: float, b2: float,
                eps: float, lrt_buf: Optional[torch.Tensor] = None) -> None:
     if W.is_cuda:
-        if lrt_buf is None:
-            lrt_buf = torch.tensor([tf1_lr_t(lr, b1, b2, t)],
-                                   dtype=torch.float32, device=W.device)
+        lrt_buf = _lrt_buf(lrt_buf, W, t, lr, b1, b2)
         native().adam_dense(W, m, v, grad, lrt_buf, float(b1), float(b2),
                             float(eps))
         return

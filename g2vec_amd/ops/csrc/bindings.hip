@@ -10,16 +10,36 @@
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "g2vec_kernels.hip"
 
-#define CHECK_DEV(x) TORCH_CHECK((x).is_cuda(), #x " must be on the GPU")
-#define CHECK_CONT(x) TORCH_CHECK((x).is_contiguous(), #x " must be contiguous")
-#define CHECK_I32(x) TORCH_CHECK((x).scalar_type() == at::kInt, #x " must be int32")
-#define CHECK_F32(x) TORCH_CHECK((x).scalar_type() == at::kFloat, #x " must be float32")
-
 namespace {
+
+// Every tensor a kernel dereferences passes one of these first: on the GPU,
+// contiguous, and (CHECK_F32 / CHECK_I32) of the dtype its data_ptr is
+// taken as. The message names the argument.
+inline void check_gpu_cont(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+inline void check_f32(const torch::Tensor& t, const char* name) {
+  check_gpu_cont(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
+}
+inline void check_i32(const torch::Tensor& t, const char* name) {
+  check_gpu_cont(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
+}
+#define CHECK_GPU_CONT(x) check_gpu_cont((x), #x)
+#define CHECK_F32(x) check_f32((x), #x)
+#define CHECK_I32(x) check_i32((x), #x)
+
+inline torch::TensorOptions opts_on(const torch::Tensor& t,
+                                    at::ScalarType dtype = at::kFloat) {
+  return torch::TensorOptions().dtype(dtype).device(t.device());
+}
 
 hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
@@ -32,6 +52,15 @@ inline int grid_for(long long work_items, int per_block) {
   return (int)blocks;
 }
 
+// Integer env knob with a default, read on EVERY call (the tests flip the
+// knobs inside one process). Clamped to >= 1: a malformed value must not
+// 0-block-launch.
+inline int env_int_min1(const char* name, int dflt) {
+  const char* e = getenv(name);
+  const int v = e ? atoi(e) : dflt;
+  return v < 1 ? 1 : v;
+}
+
 #define LAUNCH_CHECK()                                                       \
   do {                                                                       \
     hipError_t err = hipGetLastError();                                      \
@@ -39,23 +68,48 @@ inline int grid_for(long long work_items, int per_block) {
                 hipGetErrorString(err));                                     \
   } while (0)
 
+// Template-parameter dispatch: f is a generic lambda called with a
+// std::integral_constant, so f's body names the kernel instantiation once.
+// hpl = hidden / 64 columns per lane (gather/GEMV kernels), validated here.
+inline int hpl_for(int h) {
+  const int hpl = h / 64;
+  TORCH_CHECK(h % 64 == 0 && hpl >= 1 && hpl <= 16 && (hpl & (hpl - 1)) == 0,
+              "hidden must be 64*{1,2,4,8,16}");
+  return hpl;
+}
+
+template <typename F>
+void dispatch_hpl(int hpl, F&& f) {
+  switch (hpl) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+  }
+}
+
+template <typename F>
+void dispatch_cpt(int cpt, F&& f) {
+  switch (cpt) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
 // ------------------------------------------------------------------ walks
 std::vector<torch::Tensor> random_walks(torch::Tensor row_ptr, torch::Tensor col_idx,
                                         torch::Tensor weights, torch::Tensor sources,
                                         int64_t num_repetition, int64_t len_path,
                                         int64_t seed) {
-  CHECK_DEV(row_ptr); CHECK_CONT(row_ptr); CHECK_I32(row_ptr);
-  CHECK_DEV(col_idx); CHECK_CONT(col_idx); CHECK_I32(col_idx);
-  CHECK_DEV(weights); CHECK_CONT(weights); CHECK_F32(weights);
-  CHECK_DEV(sources); CHECK_CONT(sources); CHECK_I32(sources);
+  CHECK_I32(row_ptr); CHECK_I32(col_idx); CHECK_F32(weights); CHECK_I32(sources);
   TORCH_CHECK(len_path >= 1 && len_path <= 512, "len_path out of range");
   const long long n_src = sources.numel();
   const long long n_walks = n_src * num_repetition;
-  auto opts_i = torch::TensorOptions().dtype(at::kInt).device(row_ptr.device());
-  auto opts_l = torch::TensorOptions().dtype(at::kLong).device(row_ptr.device());
-  auto nodes = torch::empty({n_walks, len_path}, opts_i);
-  auto lengths = torch::empty({n_walks}, opts_i);
-  auto hashes = torch::empty({n_walks}, opts_l);
+  auto nodes = torch::empty({n_walks, len_path}, opts_on(row_ptr, at::kInt));
+  auto lengths = torch::empty({n_walks}, opts_on(row_ptr, at::kInt));
+  auto hashes = torch::empty({n_walks}, opts_on(row_ptr, at::kLong));
   if (n_walks == 0) return {nodes, lengths, hashes};
   int tsize = 256;                   // LDS hash set: >= 2x path length, pow2
   while (tsize < 2 * (int)len_path) tsize <<= 1;
@@ -77,15 +131,11 @@ std::vector<torch::Tensor> random_walks(torch::Tensor row_ptr, torch::Tensor col
 std::vector<torch::Tensor> cbow_fwd_scalar(torch::Tensor s, torch::Tensor genes,
                                            torch::Tensor offs, torch::Tensor labels,
                                            double inv_b, bool want_grad) {
-  CHECK_DEV(s); CHECK_CONT(s); CHECK_F32(s);
-  CHECK_DEV(genes); CHECK_CONT(genes); CHECK_I32(genes);
-  CHECK_DEV(offs); CHECK_CONT(offs); CHECK_I32(offs);
-  CHECK_DEV(labels); CHECK_CONT(labels); CHECK_F32(labels);
+  CHECK_F32(s); CHECK_I32(genes); CHECK_I32(offs); CHECK_F32(labels);
   const long long P = labels.numel();
-  auto opts = torch::TensorOptions().dtype(at::kFloat).device(s.device());
-  auto loss = torch::empty({P}, opts);
-  auto correct = torch::empty({P}, opts);
-  auto dO = want_grad ? torch::empty({P}, opts) : torch::empty({0}, opts);
+  auto loss = torch::empty({P}, opts_on(s));
+  auto correct = torch::empty({P}, opts_on(s));
+  auto dO = torch::empty({want_grad ? P : 0}, opts_on(s));
   if (P == 0) return {loss, correct, dO};
   int grid = grid_for(P, 16);        // 16 paths per block (16-lane sub-waves)
   if (grid > 2048) grid = 2048;      // dispatch ramp of 8k+ tiny blocks costs
@@ -100,20 +150,26 @@ std::vector<torch::Tensor> cbow_fwd_scalar(torch::Tensor s, torch::Tensor genes,
   return {loss, correct, dO};
 }
 
+// second pass of every eval: one block folds the [grid, 2] per-block count
+// partials into counts[2]
+void fold_partials(const torch::Tensor& partials, torch::Tensor& counts) {
+  hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0,
+                     cur_stream(), partials.data_ptr<float>(),
+                     (int)partials.size(0), counts.data_ptr<float>());
+  LAUNCH_CHECK();
+}
+
 void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
                        torch::Tensor labels, int64_t p_split,
                        torch::Tensor counts,
                        std::optional<torch::Tensor> dO, double inv_b) {
   if (dO) {
-    CHECK_DEV(*dO); CHECK_CONT(*dO); CHECK_F32(*dO);
+    CHECK_F32(*dO);
     TORCH_CHECK(dO->numel() >= p_split,
                 "dO must cover the train split (p < p_split)");
   }
-  CHECK_DEV(s); CHECK_CONT(s); CHECK_F32(s);
-  CHECK_DEV(genes); CHECK_CONT(genes); CHECK_I32(genes);
-  CHECK_DEV(offs); CHECK_CONT(offs); CHECK_I32(offs);
-  CHECK_DEV(labels); CHECK_CONT(labels); CHECK_F32(labels);
-  CHECK_DEV(counts); CHECK_CONT(counts); CHECK_F32(counts);
+  CHECK_F32(s); CHECK_I32(genes); CHECK_I32(offs); CHECK_F32(labels);
+  CHECK_F32(counts);
   TORCH_CHECK(counts.numel() == 2, "counts must have 2 elements");
   const long long P = labels.numel();
   if (P == 0) return;
@@ -129,45 +185,30 @@ void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
   const long long G = s.numel();
   const char* lds_env = getenv("G2VEC_EVAL_LDS");
   const long long lds_cap = lds_env ? atoll(lds_env) : 0;
-  if (G * 4 <= lds_cap && G * 4 <= 158 * 1024) {   // 160 KB LDS hard limit
-    const char* ge = getenv("G2VEC_EVAL_LDS_GRID");
-    int grid = grid_for(P, 16);
-    int gcap = ge ? atoi(ge) : 1024;
-    if (gcap < 1) gcap = 1;         // malformed env must not 0-block-launch
-    if (grid > gcap) grid = gcap;
-    auto partials = torch::empty({grid, 2},
-        torch::TensorOptions().dtype(at::kFloat).device(s.device()));
+  const bool lds = G * 4 <= lds_cap && G * 4 <= 158 * 1024;   // 160 KB LDS hard limit
+  int grid = grid_for(P, 16);       // 16 paths per block (16-lane sub-waves)
+  // G2VEC_EVAL_GRID: sweep knob; default 8192 waves fill the chip
+  const int gcap = lds ? env_int_min1("G2VEC_EVAL_LDS_GRID", 1024)
+                       : env_int_min1("G2VEC_EVAL_GRID", 2048);
+  if (grid > gcap) grid = gcap;
+  auto partials = torch::empty({grid, 2}, opts_on(s));
+  float* dOp = dO ? dO->data_ptr<float>() : nullptr;
+  if (lds) {
     hipLaunchKernelGGL(cbow_eval_counts_lds_kernel, dim3(grid),
                        dim3(256), (size_t)(G * 4), cur_stream(),
                        s.data_ptr<float>(),
                        genes.data_ptr<int>(), offs.data_ptr<int>(),
                        labels.data_ptr<float>(), P, (long long)p_split,
-                       partials.data_ptr<float>(),
-                       dO ? dO->data_ptr<float>() : nullptr, (float)inv_b,
-                       (int)G);
-    hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0,
-                       cur_stream(), partials.data_ptr<float>(), grid,
-                       counts.data_ptr<float>());
-    LAUNCH_CHECK();
-    return;
+                       partials.data_ptr<float>(), dOp, (float)inv_b, (int)G);
+  } else {
+    hipLaunchKernelGGL(cbow_eval_counts_kernel, dim3(grid),
+                       dim3(256), 0, cur_stream(), s.data_ptr<float>(),
+                       genes.data_ptr<int>(), offs.data_ptr<int>(),
+                       labels.data_ptr<float>(), P, (long long)p_split,
+                       partials.data_ptr<float>(), dOp, (float)inv_b);
   }
-  int grid = grid_for(P, 16);       // 16 paths per block (16-lane sub-waves)
-  const char* gge = getenv("G2VEC_EVAL_GRID");   // sweep knob; default
-  int gcap2 = gge ? atoi(gge) : 2048;            // 8192 waves fill the chip
-  if (gcap2 < 1) gcap2 = 1;
-  if (grid > gcap2) grid = gcap2;
-  auto partials = torch::empty({grid, 2},
-      torch::TensorOptions().dtype(at::kFloat).device(s.device()));
-  hipLaunchKernelGGL(cbow_eval_counts_kernel, dim3(grid),
-                     dim3(256), 0, cur_stream(), s.data_ptr<float>(),
-                     genes.data_ptr<int>(), offs.data_ptr<int>(),
-                     labels.data_ptr<float>(), P, (long long)p_split,
-                     partials.data_ptr<float>(),
-                     dO ? dO->data_ptr<float>() : nullptr, (float)inv_b);
-  hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0,
-                     cur_stream(), partials.data_ptr<float>(), grid,
-                     counts.data_ptr<float>());
   LAUNCH_CHECK();
+  fold_partials(partials, counts);
 }
 
 void cbow_eval_scan_(torch::Tensor s, torch::Tensor genes,
@@ -177,18 +218,13 @@ void cbow_eval_scan_(torch::Tensor s, torch::Tensor genes,
                      std::optional<torch::Tensor> dO, double inv_b) {
   // instance-parallel fused eval (see eval_scan_kernel): piece buffer is
   // persistent (hipGraph-stable) and sized P * cap
-  CHECK_DEV(s); CHECK_CONT(s); CHECK_F32(s);
-  CHECK_DEV(genes); CHECK_CONT(genes); CHECK_I32(genes);
-  CHECK_DEV(pathid); CHECK_CONT(pathid); CHECK_I32(pathid);
-  CHECK_DEV(offs); CHECK_CONT(offs); CHECK_I32(offs);
-  CHECK_DEV(labels); CHECK_CONT(labels); CHECK_F32(labels);
-  CHECK_DEV(piece); CHECK_CONT(piece); CHECK_F32(piece);
-  CHECK_DEV(counts); CHECK_CONT(counts); CHECK_F32(counts);
+  CHECK_F32(s); CHECK_I32(genes); CHECK_I32(pathid); CHECK_I32(offs);
+  CHECK_F32(labels); CHECK_F32(piece); CHECK_F32(counts);
   const long long P = labels.numel();
   const long long nnz = genes.numel();
   TORCH_CHECK(piece.numel() >= P * cap, "piece buffer too small");
   if (dO) {
-    CHECK_DEV(*dO); CHECK_CONT(*dO); CHECK_F32(*dO);
+    CHECK_F32(*dO);
     TORCH_CHECK(dO->numel() >= p_split, "dO must cover the train split");
   }
   if (P == 0) return;
@@ -207,19 +243,17 @@ void cbow_eval_scan_(torch::Tensor s, torch::Tensor genes,
                      genes.data_ptr<int>(), pathid.data_ptr<int>(),
                      offs.data_ptr<int>(), nnz, (int)cap,
                      piece.data_ptr<float>(), g_lds);
+  LAUNCH_CHECK();
   int grid_b = grid_for(P, 256);
   if (grid_b > 2048) grid_b = 2048;
-  auto partials = torch::empty({grid_b, 2},
-      torch::TensorOptions().dtype(at::kFloat).device(s.device()));
+  auto partials = torch::empty({grid_b, 2}, opts_on(s));
   hipLaunchKernelGGL(eval_finish_kernel, dim3(grid_b), dim3(256), 0,
                      cur_stream(), piece.data_ptr<float>(),
                      offs.data_ptr<int>(), labels.data_ptr<float>(), P,
                      (long long)p_split, (int)cap, partials.data_ptr<float>(),
                      dO ? dO->data_ptr<float>() : nullptr, (float)inv_b);
-  hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0,
-                     cur_stream(), partials.data_ptr<float>(), grid_b,
-                     counts.data_ptr<float>());
   LAUNCH_CHECK();
+  fold_partials(partials, counts);
 }
 
 void scatter_dO_det_(torch::Tensor inst_path, torch::Tensor seg_start,
@@ -229,11 +263,8 @@ void scatter_dO_det_(torch::Tensor inst_path, torch::Tensor seg_start,
   // ADDED into c (caller zeroes it once). The slab-blocked caller issues
   // one launch per ~3 MB dO slice so each XCD's L2 holds the slice being
   // gathered instead of thrashing across the whole dO table.
-  CHECK_DEV(inst_path); CHECK_CONT(inst_path); CHECK_I32(inst_path);
-  CHECK_DEV(seg_start); CHECK_CONT(seg_start); CHECK_I32(seg_start);
-  CHECK_DEV(seg_gene); CHECK_CONT(seg_gene); CHECK_I32(seg_gene);
-  CHECK_DEV(dO); CHECK_CONT(dO); CHECK_F32(dO);
-  CHECK_DEV(c); CHECK_CONT(c); CHECK_F32(c);
+  CHECK_I32(inst_path); CHECK_I32(seg_start); CHECK_I32(seg_gene);
+  CHECK_F32(dO); CHECK_F32(c);
   const long long n_seg = seg_gene.numel();
   if (n_seg == 0) return;
   hipLaunchKernelGGL(scatter_do_det_kernel, dim3(grid_for(n_seg, 4)), dim3(256),
@@ -246,20 +277,16 @@ void scatter_dO_det_(torch::Tensor inst_path, torch::Tensor seg_start,
 torch::Tensor scatter_dO_det(torch::Tensor inst_path, torch::Tensor seg_start,
                              torch::Tensor seg_gene, torch::Tensor dO,
                              int64_t n_genes) {
-  CHECK_DEV(inst_path); CHECK_CONT(inst_path); CHECK_I32(inst_path);
-  CHECK_DEV(seg_start); CHECK_CONT(seg_start); CHECK_I32(seg_start);
-  CHECK_DEV(seg_gene); CHECK_CONT(seg_gene); CHECK_I32(seg_gene);
-  CHECK_DEV(dO); CHECK_CONT(dO); CHECK_F32(dO);
-  auto c = torch::zeros({n_genes},
-                        torch::TensorOptions().dtype(at::kFloat).device(dO.device()));
-  const long long n_seg = seg_gene.numel();
-  if (n_seg == 0) return c;
-  hipLaunchKernelGGL(scatter_do_det_kernel, dim3(grid_for(n_seg, 4)), dim3(256),
-                     0, cur_stream(), inst_path.data_ptr<int>(),
-                     seg_start.data_ptr<int>(), seg_gene.data_ptr<int>(),
-                     (int)n_seg, dO.data_ptr<float>(), c.data_ptr<float>());
-  LAUNCH_CHECK();
+  auto c = torch::zeros({n_genes}, opts_on(dO));
+  scatter_dO_det_(inst_path, seg_start, seg_gene, dO, c);
   return c;
+}
+
+// lr_t lives in a device slot (see adam_rank1_kernel); only element 0 is read
+inline void check_lrt(const torch::Tensor& lrt) {
+  TORCH_CHECK(lrt.is_cuda(), "lrt must be on the GPU");
+  TORCH_CHECK(lrt.scalar_type() == at::kFloat, "lrt must be float32");
+  TORCH_CHECK(lrt.numel() >= 1, "lrt must hold at least one element");
 }
 
 void adam_rank1(torch::Tensor W, torch::Tensor m, torch::Tensor v,
@@ -272,24 +299,29 @@ void adam_rank1(torch::Tensor W, torch::Tensor m, torch::Tensor v,
   // of dW_ho = W_pre^T c, and one fold launch applies the who update
   // (replaces the separate gemv_cols + fold_cols + adam_dense chain and
   // its extra full W read; deterministic block order).
-  CHECK_DEV(W); CHECK_CONT(W); CHECK_F32(W);
-  CHECK_CONT(m); CHECK_CONT(v); CHECK_CONT(c); CHECK_CONT(who);
-  CHECK_DEV(lrt); CHECK_F32(lrt);
+  CHECK_F32(W); CHECK_F32(m); CHECK_F32(v); CHECK_F32(c); CHECK_F32(who);
+  check_lrt(lrt);
+  TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long G = W.size(0);
   const int h = (int)W.size(1);
-  TORCH_CHECK(h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
+  TORCH_CHECK(h >= 4 && h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
               "hidden must be a multiple of 4 with h/4 dividing 256");
+  TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
+              "m/v/W size mismatch");
+  TORCH_CHECK(c.numel() == G, "c must have one element per W row");
+  TORCH_CHECK(who.numel() == h, "who must have one element per W column");
   const int rpb = 256 / (h / 4);   // rows per 256-thread block
   const bool fused = mO.has_value();
+  TORCH_CHECK(fused == vO.has_value(), "mO and vO go together");
   int grid = grid_for(G, rpb);
   torch::Tensor partials;
   float* gw = nullptr;
   if (fused) {
-    CHECK_DEV(*mO); CHECK_CONT(*mO); CHECK_F32(*mO);
-    CHECK_DEV(*vO); CHECK_CONT(*vO); CHECK_F32(*vO);
+    CHECK_F32(*mO); CHECK_F32(*vO);
+    TORCH_CHECK(mO->numel() == h && vO->numel() == h,
+                "mO/vO must have one element per W column");
     if (grid > 1024) grid = 1024;    // bound the partial table / fold cost
-    partials = torch::empty({grid, h},
-        torch::TensorOptions().dtype(at::kFloat).device(W.device()));
+    partials = torch::empty({grid, h}, opts_on(W));
     gw = partials.data_ptr<float>();
   }
   hipLaunchKernelGGL(adam_rank1_kernel, dim3(grid), dim3(256), 0,
@@ -297,23 +329,25 @@ void adam_rank1(torch::Tensor W, torch::Tensor m, torch::Tensor v,
                      v.data_ptr<float>(), c.data_ptr<float>(),
                      who.data_ptr<float>(), G, h, lrt.data_ptr<float>(),
                      (float)b1, (float)b2, (float)eps, gw);
+  LAUNCH_CHECK();
   if (fused) {
     hipLaunchKernelGGL(fold_gw_adam_kernel, dim3(grid_for(h, 4)), dim3(256),
                        0, cur_stream(), gw, grid, h, who.data_ptr<float>(),
                        mO->data_ptr<float>(), vO->data_ptr<float>(),
                        lrt.data_ptr<float>(), (float)b1, (float)b2,
                        (float)eps);
+    LAUNCH_CHECK();
   }
-  LAUNCH_CHECK();
 }
 
 void adam_dense(torch::Tensor W, torch::Tensor m, torch::Tensor v,
                 torch::Tensor grad, torch::Tensor lrt, double b1, double b2,
                 double eps) {
-  CHECK_DEV(W); CHECK_CONT(W); CHECK_F32(W);
-  CHECK_CONT(m); CHECK_CONT(v); CHECK_CONT(grad);
-  CHECK_DEV(lrt); CHECK_F32(lrt);
+  CHECK_F32(W); CHECK_F32(m); CHECK_F32(v); CHECK_F32(grad);
+  check_lrt(lrt);
   TORCH_CHECK(grad.numel() == W.numel(), "grad/W size mismatch");
+  TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
+              "m/v/W size mismatch");
   const long long n = W.numel();
   hipLaunchKernelGGL(adam_dense_kernel, dim3(grid_for(n, 256)), dim3(256), 0,
                      cur_stream(), W.data_ptr<float>(), m.data_ptr<float>(),
@@ -327,67 +361,41 @@ std::vector<torch::Tensor> cbow_fwd(torch::Tensor W, torch::Tensor who,
                                     torch::Tensor genes, torch::Tensor offs,
                                     torch::Tensor labels, double inv_b,
                                     bool want_grad, int64_t act) {
-  CHECK_DEV(W); CHECK_CONT(W);
-  CHECK_DEV(who); CHECK_CONT(who); CHECK_F32(who);
-  CHECK_DEV(genes); CHECK_CONT(genes); CHECK_I32(genes);
-  CHECK_DEV(offs); CHECK_CONT(offs); CHECK_I32(offs);
-  CHECK_DEV(labels); CHECK_CONT(labels); CHECK_F32(labels);
+  CHECK_GPU_CONT(W);
+  CHECK_F32(who); CHECK_I32(genes); CHECK_I32(offs); CHECK_F32(labels);
   const bool bf16 = W.scalar_type() == at::kBFloat16;
   const bool fp16 = W.scalar_type() == at::kHalf;
   TORCH_CHECK(bf16 || fp16 || W.scalar_type() == at::kFloat,
               "W must be f32, bf16 or fp16");
   const long long P = labels.numel();
   const int h = (int)W.size(1);
-  const int hpl = h / 64;
-  TORCH_CHECK(h % 64 == 0 && hpl >= 1 && hpl <= 16 &&
-              (hpl & (hpl - 1)) == 0, "hidden must be 64*{1,2,4,8,16}");
-  auto opts = torch::TensorOptions().dtype(at::kFloat).device(W.device());
-  auto loss = torch::empty({P}, opts);
-  auto correct = torch::empty({P}, opts);
-  auto dO = want_grad ? torch::empty({P}, opts) : torch::empty({0}, opts);
-  auto H = want_grad ? torch::empty({P, h}, opts) : torch::empty({0}, opts);
+  const int hpl = hpl_for(h);
+  auto loss = torch::empty({P}, opts_on(W));
+  auto correct = torch::empty({P}, opts_on(W));
+  auto dO = torch::empty({want_grad ? P : 0}, opts_on(W));
+  auto H = want_grad ? torch::empty({P, h}, opts_on(W))
+                     : torch::empty({0}, opts_on(W));
   if (P == 0) return {loss, correct, dO, H};
   const int grid = grid_for(P, 4);
   float* Hp = want_grad ? H.data_ptr<float>() : nullptr;
   float* dOp = want_grad ? dO.data_ptr<float>() : nullptr;
-
-#define FWD_CASE(WT, HPL, PTR)                                                \
-  hipLaunchKernelGGL((cbow_fwd_kernel<WT, HPL>), dim3(grid), dim3(256), 0,    \
-                     cur_stream(), PTR, who.data_ptr<float>(),                \
-                     genes.data_ptr<int>(), offs.data_ptr<int>(),             \
-                     labels.data_ptr<float>(), P, (float)inv_b, h, Hp,        \
-                     loss.data_ptr<float>(), correct.data_ptr<float>(), dOp,  \
-                     (int)act)
-  if (bf16) {
-    const bf16_bits* Wp = (const bf16_bits*)W.data_ptr<at::BFloat16>();
-    switch (hpl) {
-      case 1: FWD_CASE(bf16_bits, 1, Wp); break;
-      case 2: FWD_CASE(bf16_bits, 2, Wp); break;
-      case 4: FWD_CASE(bf16_bits, 4, Wp); break;
-      case 8: FWD_CASE(bf16_bits, 8, Wp); break;
-      default: FWD_CASE(bf16_bits, 16, Wp); break;
-    }
-  } else if (fp16) {
-    const fp16_bits* Wp = (const fp16_bits*)W.data_ptr<at::Half>();
-    switch (hpl) {
-      case 1: FWD_CASE(fp16_bits, 1, Wp); break;
-      case 2: FWD_CASE(fp16_bits, 2, Wp); break;
-      case 4: FWD_CASE(fp16_bits, 4, Wp); break;
-      case 8: FWD_CASE(fp16_bits, 8, Wp); break;
-      default: FWD_CASE(fp16_bits, 16, Wp); break;
-    }
-  } else {
-    const float* Wp = W.data_ptr<float>();
-    switch (hpl) {
-      case 1: FWD_CASE(float, 1, Wp); break;
-      case 2: FWD_CASE(float, 2, Wp); break;
-      case 4: FWD_CASE(float, 4, Wp); break;
-      case 8: FWD_CASE(float, 8, Wp); break;
-      default: FWD_CASE(float, 16, Wp); break;
-    }
-  }
-#undef FWD_CASE
-  LAUNCH_CHECK();
+  // Wp: the weight table as the kernel's element (tag) type
+  auto launch = [&](auto* Wp) {
+    using WT = std::remove_cv_t<std::remove_pointer_t<decltype(Wp)>>;
+    dispatch_hpl(hpl, [&](auto HPL) {
+      hipLaunchKernelGGL((cbow_fwd_kernel<WT, decltype(HPL)::value>),
+                         dim3(grid), dim3(256), 0, cur_stream(),
+                         (const WT*)Wp, who.data_ptr<float>(),
+                         genes.data_ptr<int>(), offs.data_ptr<int>(),
+                         labels.data_ptr<float>(), P, (float)inv_b, h, Hp,
+                         loss.data_ptr<float>(), correct.data_ptr<float>(),
+                         dOp, (int)act);
+      LAUNCH_CHECK();
+    });
+  };
+  if (bf16) launch((const bf16_bits*)W.data_ptr<at::BFloat16>());
+  else if (fp16) launch((const fp16_bits*)W.data_ptr<at::Half>());
+  else launch(W.data_ptr<float>());
   return {loss, correct, dO, H};
 }
 
@@ -396,49 +404,34 @@ torch::Tensor cbow_bwd_rows(torch::Tensor who, torch::Tensor inst_path,
                             torch::Tensor dO, int64_t n_genes,
                             std::optional<torch::Tensor> Hpre) {
   // Hpre: pre-activation H for the ReLU backward mask (absent = linear)
-  CHECK_DEV(who); CHECK_CONT(who); CHECK_F32(who);
-  CHECK_DEV(inst_path); CHECK_CONT(inst_path); CHECK_I32(inst_path);
-  CHECK_DEV(seg_start); CHECK_CONT(seg_start); CHECK_I32(seg_start);
-  CHECK_DEV(seg_gene); CHECK_CONT(seg_gene); CHECK_I32(seg_gene);
-  CHECK_DEV(dO); CHECK_CONT(dO); CHECK_F32(dO);
-  if (Hpre) { CHECK_DEV(*Hpre); CHECK_CONT(*Hpre); CHECK_F32(*Hpre); }
+  CHECK_F32(who); CHECK_I32(inst_path); CHECK_I32(seg_start);
+  CHECK_I32(seg_gene); CHECK_F32(dO);
+  if (Hpre) CHECK_F32(*Hpre);
   const int h = (int)who.numel();
-  const int hpl = h / 64;
-  TORCH_CHECK(h % 64 == 0 && hpl >= 1 && hpl <= 16 &&
-              (hpl & (hpl - 1)) == 0, "hidden must be 64*{1,2,4,8,16}");
-  auto dW = torch::zeros({n_genes, h},
-                         torch::TensorOptions().dtype(at::kFloat).device(dO.device()));
+  const int hpl = hpl_for(h);
+  auto dW = torch::zeros({n_genes, h}, opts_on(dO));
   const int n_seg = (int)seg_gene.numel();
   if (n_seg == 0) return dW;
   const int grid = grid_for(n_seg, 4);
-#define BWD_CASE(HPL)                                                         \
-  hipLaunchKernelGGL((cbow_bwd_rows_det_kernel<HPL>), dim3(grid), dim3(256),  \
-                     0, cur_stream(), who.data_ptr<float>(),                  \
-                     inst_path.data_ptr<int>(), seg_start.data_ptr<int>(),    \
-                     seg_gene.data_ptr<int>(), n_seg,                         \
-                     dO.data_ptr<float>(), h, dW.data_ptr<float>(),           \
-                     Hpre ? Hpre->data_ptr<float>() : nullptr)
-  switch (hpl) {
-    case 1: BWD_CASE(1); break;
-    case 2: BWD_CASE(2); break;
-    case 4: BWD_CASE(4); break;
-    case 8: BWD_CASE(8); break;
-    default: BWD_CASE(16); break;
-  }
-#undef BWD_CASE
-  LAUNCH_CHECK();
+  dispatch_hpl(hpl, [&](auto HPL) {
+    hipLaunchKernelGGL((cbow_bwd_rows_det_kernel<decltype(HPL)::value>),
+                       dim3(grid), dim3(256), 0, cur_stream(),
+                       who.data_ptr<float>(), inst_path.data_ptr<int>(),
+                       seg_start.data_ptr<int>(), seg_gene.data_ptr<int>(),
+                       n_seg, dO.data_ptr<float>(), h, dW.data_ptr<float>(),
+                       Hpre ? Hpre->data_ptr<float>() : nullptr);
+    LAUNCH_CHECK();
+  });
   return dW;
 }
 
 // ------------------------------------------------------------------- PCC
 torch::Tensor pcc_edges(torch::Tensor zt, torch::Tensor edge_idx,
                         int64_t n_group) {
-  CHECK_DEV(zt); CHECK_CONT(zt); CHECK_F32(zt);
-  CHECK_DEV(edge_idx); CHECK_CONT(edge_idx); CHECK_I32(edge_idx);
+  CHECK_F32(zt); CHECK_I32(edge_idx);
   const long long E = edge_idx.size(0);
   const int S = (int)zt.size(1);
-  auto out = torch::empty({E},
-                          torch::TensorOptions().dtype(at::kFloat).device(zt.device()));
+  auto out = torch::empty({E}, opts_on(zt));
   if (E == 0) return out;
   hipLaunchKernelGGL(pcc_edges_kernel, dim3(grid_for(E, 4)), dim3(256), 0,
                      cur_stream(), zt.data_ptr<float>(),
@@ -449,7 +442,7 @@ torch::Tensor pcc_edges(torch::Tensor zt, torch::Tensor edge_idx,
 }
 
 torch::Tensor corr_gemm(torch::Tensor zt, int64_t n_group) {
-  CHECK_DEV(zt); CHECK_CONT(zt); CHECK_F32(zt);
+  CHECK_F32(zt);
   // the kernel body is compiled only for gfx950 (MFMA builtins): on any
   // other arch the launch would be a no-op returning uninitialized C —
   // trap here instead of silently emitting garbage PCC weights
@@ -468,8 +461,7 @@ torch::Tensor corr_gemm(torch::Tensor zt, int64_t n_group) {
   const size_t lds = 2ull * 64 * S4 * sizeof(float);
   TORCH_CHECK(lds <= 160 * 1024,
               "corr_gemm: S too large for the LDS-staged tile (use pcc_mode=edge)");
-  auto C = torch::empty({G, G},
-                        torch::TensorOptions().dtype(at::kFloat).device(zt.device()));
+  auto C = torch::empty({G, G}, opts_on(zt));
   const int ntile = (G + 63) / 64;
   hipLaunchKernelGGL(corr_gemm_kernel, dim3(ntile * ntile), dim3(256), lds,
                      cur_stream(), zt.data_ptr<float>(), C.data_ptr<float>(),
@@ -479,7 +471,7 @@ torch::Tensor corr_gemm(torch::Tensor zt, int64_t n_group) {
 }
 
 void trunc_normal_(torch::Tensor out, double std, int64_t seed) {
-  CHECK_DEV(out); CHECK_CONT(out); CHECK_F32(out);
+  CHECK_F32(out);
   const long long n = (long long)out.numel();
   if (n == 0) return;
   hipLaunchKernelGGL(trunc_normal_kernel, dim3(grid_for(n, 256)), dim3(256),
@@ -489,36 +481,23 @@ void trunc_normal_(torch::Tensor out, double std, int64_t seed) {
 }
 
 void gemv_rows_(torch::Tensor W, torch::Tensor x, torch::Tensor out) {
-  CHECK_DEV(W); CHECK_CONT(W); CHECK_F32(W);
-  CHECK_DEV(x); CHECK_CONT(x); CHECK_F32(x);
-  CHECK_DEV(out); CHECK_CONT(out); CHECK_F32(out);
+  CHECK_F32(W); CHECK_F32(x); CHECK_F32(out);
   const long long G = W.size(0);
   const int h = (int)W.size(1);
-  const int hpl = h / 64;
-  TORCH_CHECK(h % 64 == 0 && hpl >= 1 && hpl <= 16 && (hpl & (hpl - 1)) == 0,
-              "hidden must be 64*{1,2,4,8,16}");
+  const int hpl = hpl_for(h);
   TORCH_CHECK(out.numel() == G && x.numel() == h, "gemv_rows shape mismatch");
   int grid = grid_for(G, 4);
   if (grid > 8192) grid = 8192;
-#define GEMVR_CASE(HPL)                                                       \
-  hipLaunchKernelGGL((gemv_rows_kernel<HPL>), dim3(grid), dim3(256), 0,       \
-                     cur_stream(), W.data_ptr<float>(), x.data_ptr<float>(),  \
-                     G, h, out.data_ptr<float>())
-  switch (hpl) {
-    case 1: GEMVR_CASE(1); break;
-    case 2: GEMVR_CASE(2); break;
-    case 4: GEMVR_CASE(4); break;
-    case 8: GEMVR_CASE(8); break;
-    default: GEMVR_CASE(16); break;
-  }
-#undef GEMVR_CASE
-  LAUNCH_CHECK();
+  dispatch_hpl(hpl, [&](auto HPL) {
+    hipLaunchKernelGGL((gemv_rows_kernel<decltype(HPL)::value>), dim3(grid),
+                       dim3(256), 0, cur_stream(), W.data_ptr<float>(),
+                       x.data_ptr<float>(), G, h, out.data_ptr<float>());
+    LAUNCH_CHECK();
+  });
 }
 
 void gemv_cols_(torch::Tensor W, torch::Tensor c, torch::Tensor out) {
-  CHECK_DEV(W); CHECK_CONT(W); CHECK_F32(W);
-  CHECK_DEV(c); CHECK_CONT(c); CHECK_F32(c);
-  CHECK_DEV(out); CHECK_CONT(out); CHECK_F32(out);
+  CHECK_F32(W); CHECK_F32(c); CHECK_F32(out);
   const long long G = W.size(0);
   const int h = (int)W.size(1);
   const int cpt = (h >= 256) ? h / 256 : 1;
@@ -530,18 +509,13 @@ void gemv_cols_(torch::Tensor W, torch::Tensor c, torch::Tensor out) {
   int grid = (int)((G + 7) / 8);
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
-  auto partials = torch::empty({grid, h},
-      torch::TensorOptions().dtype(at::kFloat).device(W.device()));
-#define GEMVC_CASE(CPT)                                                       \
-  hipLaunchKernelGGL((gemv_cols_kernel<CPT>), dim3(grid), dim3(256), 0,       \
-                     cur_stream(), W.data_ptr<float>(), c.data_ptr<float>(),  \
-                     G, h, partials.data_ptr<float>())
-  switch (cpt) {
-    case 1: GEMVC_CASE(1); break;
-    case 2: GEMVC_CASE(2); break;
-    default: GEMVC_CASE(4); break;
-  }
-#undef GEMVC_CASE
+  auto partials = torch::empty({grid, h}, opts_on(W));
+  dispatch_cpt(cpt, [&](auto CPT) {
+    hipLaunchKernelGGL((gemv_cols_kernel<decltype(CPT)::value>), dim3(grid),
+                       dim3(256), 0, cur_stream(), W.data_ptr<float>(),
+                       c.data_ptr<float>(), G, h, partials.data_ptr<float>());
+    LAUNCH_CHECK();
+  });
   hipLaunchKernelGGL(fold_cols_kernel, dim3((h + 3) / 4), dim3(256), 0,
                      cur_stream(), partials.data_ptr<float>(), grid, h,
                      out.data_ptr<float>());
@@ -549,13 +523,13 @@ void gemv_cols_(torch::Tensor W, torch::Tensor c, torch::Tensor out) {
 }
 
 torch::Tensor bf16_copy(torch::Tensor src) {
-  CHECK_DEV(src); CHECK_CONT(src); CHECK_F32(src);
+  CHECK_F32(src);
   auto out = torch::empty_like(src, src.options().dtype(at::kBFloat16));
   const long long n = src.numel();
-  if (n)
-    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n, 256)), dim3(256),
-                       0, cur_stream(), src.data_ptr<float>(),
-                       (uint16_t*)out.data_ptr<at::BFloat16>(), n);
+  if (n == 0) return out;
+  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n, 256)), dim3(256),
+                     0, cur_stream(), src.data_ptr<float>(),
+                     (uint16_t*)out.data_ptr<at::BFloat16>(), n);
   LAUNCH_CHECK();
   return out;
 }

@@ -3,22 +3,29 @@
 // Hand-written HIP; no CUDA compatibility layers. Wavefront = 64 lanes
 // throughout. Kernels (SURVEY 2.10 K-table in parentheses):
 //
-//   walk_kernel            (K10) CSR biased non-revisiting random walk,
-//                          one wave per walk, LDS visited list, counter-based
-//                          splitmix64 RNG (bit-identical to ops/cpu_ref.py)
-//   cbow_fwd_scalar_kernel (K1+K2+K3+K8 collapsed) o_p = sum s_g over the
-//                          path + fused sigmoid-CE loss/accuracy/dlogit
-//   scatter_do_det_kernel  (K6 collapsed) c = X^T dO by gene-sorted segments
-//                          — deterministic (no atomics)
-//   adam_rank1_kernel      (K7) dense TF1-Adam with rank-1 grad c (x) who
-//   adam_dense_kernel      (K7) dense TF1-Adam with materialized grad
-//   cbow_fwd_kernel        (K1+K2+K3+K8 general) row-gather forward,
-//                          bf16/f32 W_ih, fp32 accumulate, H stored
-//   cbow_bwd_rows_det_kernel (K6 general) per-gene-segment dH-row reduce
-//                          (deterministic, atomic-free)
-//   pcc_edges_kernel       (K11) per-edge PCC dot product over samples
-//   corr_gemm_kernel       (K11 dense path) C = Z Z^T / S on f32 MFMA
-//                          (v_mfma_f32_16x16x4_f32) with LDS-staged tiles
+//   walk_kernel                 (K10) biased non-revisiting CSR walk, wave per walk, LDS hash-set visited
+//   cbow_fwd_scalar_kernel      (K1+K2+K3+K8 collapsed) o_p = sum s_g + sigmoid-CE loss/correct/dlogit
+//   cbow_eval_counts_kernel     fused eval: per-split correct counts + next-epoch train dlogits
+//   cbow_eval_counts_lds_kernel same body with the s table staged in LDS (opt-in)
+//   fold_partials_kernel        one-block fold of [n_blocks, 2] count partials
+//   scatter_do_det_kernel       (K6 collapsed) c = X^T dO by gene-sorted segments, atomic-free
+//   adam_rank1_kernel           (K7) TF1 Adam, rank-1 grad c (x) who; optional dW_ho partials
+//   fold_gw_adam_kernel         folds those partials and applies the W_ho Adam update
+//   adam_dense_kernel           (K7) TF1 Adam, materialized grad
+//   cbow_fwd_kernel<WT,HPL>     (K1+K2+K3+K8 general) row-gather forward, f32/bf16/fp16 W_ih, H stored
+//   cbow_bwd_rows_det_kernel<HPL> (K6 general) per-gene-segment dW row reduce, atomic-free
+//   pcc_edges_kernel            (K11) per-edge |PCC| dot product over samples
+//   corr_gemm_kernel            (K11 dense) C = Z Z^T / S on v_mfma_f32_16x16x4_f32, LDS tiles
+//   gemv_rows_kernel<HPL>       s = W @ x, wave per row
+//   gemv_cols_kernel<CPT>       per-block partials of W^T c
+//   fold_cols_kernel            folds the gemv_cols partials, wave per column
+//   f32_to_bf16_kernel          round-to-nearest-even cast, NaN kept quiet
+//   trunc_normal_kernel         (K9) seeded +-2 sigma truncated-normal fill
+//   eval_scan_kernel            instance-parallel eval: segmented scan to per-window piece sums
+//   eval_finish_kernel          thread-per-path fold of the pieces, counts + train dlogits
+//
+// The templates are instantiated by their launch sites in bindings.hip, the
+// one translation unit that includes this file.
 //
 // Reference behaviour being reimplemented (not copied): mathcom/G2Vec
 // G2Vec.py:328-346 (walk), :238-251 (CBOW fwd/loss/acc), :245-246 (Adam),
@@ -88,6 +95,24 @@ __device__ __forceinline__ float wave_incl_scan(float v) {
     if (lane >= o) v += t;
   }
   return v;
+}
+
+// fold two per-thread accumulators over a 256-thread block (wave-reduce,
+// then 4 wave slots in LDS); thread 0 writes the two totals to out2[0..1].
+// The one fold order every count kernel shares.
+__device__ __forceinline__ void block_fold2(float c0, float c1,
+                                            float* __restrict__ out2) {
+  c0 = wave_sum(c0);
+  c1 = wave_sum(c1);
+  __shared__ float sm[8];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = threadIdx.x >> 6;
+  if (lane == 0) { sm[wib] = c0; sm[4 + wib] = c1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    out2[0] = sm[0] + sm[1] + sm[2] + sm[3];
+    out2[1] = sm[4] + sm[5] + sm[6] + sm[7];
+  }
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t b) {
@@ -362,6 +387,18 @@ __device__ __forceinline__ float subwave_sum16(float v) {
   return v;                       // every lane of the 16-group has the sum
 }
 
+// The per-path epilogue, in one place: the CPU oracle matches these three
+// expressions bit for bit, and the fast and general paths must not fork.
+__device__ __forceinline__ float sigmoid_ce(float o, float y) {
+  return fmaxf(o, 0.f) - o * y + log1pf(expf(-fabsf(o)));
+}
+__device__ __forceinline__ float is_correct(float o, float y) {
+  return ((o > 0.f ? 1.f : 0.f) == y) ? 1.f : 0.f;
+}
+__device__ __forceinline__ float dlogit(float o, float y, float inv_b) {
+  return (1.f / (1.f + expf(-o)) - y) * inv_b;
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 cbow_fwd_scalar_kernel(const float* __restrict__ s, const int* __restrict__ genes,
                        const int* __restrict__ offs, const float* __restrict__ labels,
@@ -378,9 +415,9 @@ cbow_fwd_scalar_kernel(const float* __restrict__ s, const int* __restrict__ gene
     const float o = subwave_sum16(partial);
     if (sublane == 0) {
       const float y = labels[p];
-      loss[p] = fmaxf(o, 0.f) - o * y + log1pf(expf(-fabsf(o)));
-      correct[p] = ((o > 0.f ? 1.f : 0.f) == y) ? 1.f : 0.f;
-      if (dO) dO[p] = (1.f / (1.f + expf(-o)) - y) * inv_b;
+      loss[p] = sigmoid_ce(o, y);
+      correct[p] = is_correct(o, y);
+      if (dO) dO[p] = dlogit(o, y, inv_b);
     }
   }
 }
@@ -389,15 +426,18 @@ cbow_fwd_scalar_kernel(const float* __restrict__ s, const int* __restrict__ gene
 // counts (train = paths < p_split of the concatenated set, val = rest)
 // accumulate per wave, reduce in-block, and write ATOMIC-FREE per-block
 // partials; a one-block second pass folds them (a same-two-words atomic
-// fan-in measured ~11 ns per serialized add — 10k blocks cost 200 us)
-extern "C" __global__ void __launch_bounds__(256)
-cbow_eval_counts_kernel(const float* __restrict__ s, const int* __restrict__ genes,
-                        const int* __restrict__ offs, const float* __restrict__ labels,
-                        long long P, long long p_split,
-                        float* __restrict__ partials,
-                        float* __restrict__ dO, float inv_b) {
+// fan-in measured ~11 ns per serialized add — 10k blocks cost 200 us).
+// One body for both entry points below: st is the s table, in global
+// memory or staged in LDS, and everything else — per-path math and
+// accumulation order — is the same code, hence bitwise-equal outputs.
+// subs_per_block = blockDim.x / SUBW is read by the entry point: only in a
+// __global__ function does the compiler fold blockDim to one scalar load.
+__device__ __forceinline__ void
+eval_counts_body(const float* __restrict__ st, const int* __restrict__ genes,
+                 const int* __restrict__ offs, const float* __restrict__ labels,
+                 long long P, long long p_split, float* __restrict__ partials,
+                 float* __restrict__ dO, float inv_b, int subs_per_block) {
   const int sublane = threadIdx.x & (SUBW - 1);
-  const int subs_per_block = blockDim.x / SUBW;
   const int sub = threadIdx.x / SUBW;
   float c0 = 0.f, c1 = 0.f;                    // sublane-0 accumulators
   for (long long p = (long long)blockIdx.x * subs_per_block + sub; p < P;
@@ -405,33 +445,30 @@ cbow_eval_counts_kernel(const float* __restrict__ s, const int* __restrict__ gen
     const int lo = offs[p], hi = offs[p + 1];
     float partial = 0.f;
     for (int i = lo + sublane; i < hi; i += SUBW)
-      partial += s[__builtin_nontemporal_load(&genes[i])];
+      partial += st[__builtin_nontemporal_load(&genes[i])];
     const float o = subwave_sum16(partial);
     if (sublane == 0) {
       const float y = labels[p];
-      const float corr = (((o > 0.f ? 1.f : 0.f) == y) ? 1.f : 0.f);
+      const float corr = is_correct(o, y);
       if (p < p_split) c0 += corr; else c1 += corr;
       // fused next-epoch forward: this eval's s IS the next epoch's
       // pre-update s, so emit the train-split dO here and the standalone
       // forward kernel disappears from steady-state epochs (the s-gather
       // over the train paths runs ONCE per weight version, not twice)
-      if (dO && p < p_split)
-        dO[p] = (1.f / (1.f + expf(-o)) - y) * inv_b;
+      if (dO && p < p_split) dO[p] = dlogit(o, y, inv_b);
     }
   }
-  // fold the per-thread accumulators: sublane0 lanes hold the values;
-  // wave-reduce then block-reduce
-  c0 = wave_sum(c0);
-  c1 = wave_sum(c1);
-  __shared__ float sm[8];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wib = threadIdx.x >> 6;
-  if (lane == 0) { sm[wib] = c0; sm[4 + wib] = c1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partials[2 * blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-    partials[2 * blockIdx.x + 1] = sm[4] + sm[5] + sm[6] + sm[7];
-  }
+  block_fold2(c0, c1, partials + 2 * blockIdx.x);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+cbow_eval_counts_kernel(const float* __restrict__ s, const int* __restrict__ genes,
+                        const int* __restrict__ offs, const float* __restrict__ labels,
+                        long long P, long long p_split,
+                        float* __restrict__ partials,
+                        float* __restrict__ dO, float inv_b) {
+  eval_counts_body(s, genes, offs, labels, P, p_split, partials, dO, inv_b,
+                   blockDim.x / SUBW);
 }
 
 // LDS-staged variant: at ex_* scale the whole s table is 30 KB, but the
@@ -440,10 +477,9 @@ cbow_eval_counts_kernel(const float* __restrict__ s, const int* __restrict__ gen
 // one texture/addressing unit. Staging s in LDS turns each gather into a
 // ds_read (32-bank parallel, ~2-4x conflict factor), so the block pays
 // one coalesced G-float stage (L2-broadcast: every block reads the same
-// table) and then gathers at LDS rate. The per-path math and accumulation
-// order are IDENTICAL to cbow_eval_counts_kernel — bitwise-equal outputs;
-// the host picks this kernel when G*4 fits the LDS budget and caps the
-// grid so each resident block amortizes its stage over many paths.
+// table) and then gathers at LDS rate. The host picks this kernel when
+// G*4 fits the LDS budget and caps the grid so each resident block
+// amortizes its stage over many paths.
 extern "C" __global__ void __launch_bounds__(256)
 cbow_eval_counts_lds_kernel(const float* __restrict__ s,
                             const int* __restrict__ genes,
@@ -455,36 +491,8 @@ cbow_eval_counts_lds_kernel(const float* __restrict__ s,
   extern __shared__ float s_lds[];
   for (int g = threadIdx.x; g < G; g += blockDim.x) s_lds[g] = s[g];
   __syncthreads();
-  const int sublane = threadIdx.x & (SUBW - 1);
-  const int subs_per_block = blockDim.x / SUBW;
-  const int sub = threadIdx.x / SUBW;
-  float c0 = 0.f, c1 = 0.f;
-  for (long long p = (long long)blockIdx.x * subs_per_block + sub; p < P;
-       p += (long long)gridDim.x * subs_per_block) {
-    const int lo = offs[p], hi = offs[p + 1];
-    float partial = 0.f;
-    for (int i = lo + sublane; i < hi; i += SUBW)
-      partial += s_lds[__builtin_nontemporal_load(&genes[i])];
-    const float o = subwave_sum16(partial);
-    if (sublane == 0) {
-      const float y = labels[p];
-      const float corr = (((o > 0.f ? 1.f : 0.f) == y) ? 1.f : 0.f);
-      if (p < p_split) c0 += corr; else c1 += corr;
-      if (dO && p < p_split)
-        dO[p] = (1.f / (1.f + expf(-o)) - y) * inv_b;
-    }
-  }
-  c0 = wave_sum(c0);
-  c1 = wave_sum(c1);
-  __shared__ float sm[8];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wib = threadIdx.x >> 6;
-  if (lane == 0) { sm[wib] = c0; sm[4 + wib] = c1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partials[2 * blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-    partials[2 * blockIdx.x + 1] = sm[4] + sm[5] + sm[6] + sm[7];
-  }
+  eval_counts_body(s_lds, genes, offs, labels, P, p_split, partials, dO,
+                   inv_b, blockDim.x / SUBW);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -495,17 +503,7 @@ fold_partials_kernel(const float* __restrict__ partials, int n_blocks,
     c0 += partials[2 * b];
     c1 += partials[2 * b + 1];
   }
-  c0 = wave_sum(c0);
-  c1 = wave_sum(c1);
-  __shared__ float sm[8];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wib = threadIdx.x >> 6;
-  if (lane == 0) { sm[wib] = c0; sm[4 + wib] = c1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    counts[0] = sm[0] + sm[1] + sm[2] + sm[3];
-    counts[1] = sm[4] + sm[5] + sm[6] + sm[7];
-  }
+  block_fold2(c0, c1, counts);
 }
 
 // =============================================== fast path: c = X^T dO (det.)
@@ -707,9 +705,9 @@ cbow_fwd_kernel(const WT* __restrict__ W, const float* __restrict__ who,
     }
     if (lane == 0) {
       const float y = labels[p];
-      loss[p] = fmaxf(o, 0.f) - o * y + log1pf(expf(-fabsf(o)));
-      correct[p] = ((o > 0.f ? 1.f : 0.f) == y) ? 1.f : 0.f;
-      if (dO) dO[p] = (1.f / (1.f + expf(-o)) - y) * inv_b;
+      loss[p] = sigmoid_ce(o, y);
+      correct[p] = is_correct(o, y);
+      if (dO) dO[p] = dlogit(o, y, inv_b);
     }
   }
 }
@@ -794,8 +792,6 @@ pcc_edges_kernel(const float* __restrict__ zt, const int* __restrict__ edges,
 // rate — no xf32 on gfx950, see cdna_hip_programming.md §3). 64x64 tile per
 // 4-wave block (each wave one 32x32 sub-tile = 2x2 16x16 fragments), both
 // operand tiles staged once in LDS (K = S <= 320 fits the 160 KiB budget).
-typedef float f32x4c __attribute__((ext_vector_type(4)));
-
 extern "C" __global__ void __launch_bounds__(256)
 corr_gemm_kernel(const float* __restrict__ zt, float* __restrict__ C,
                  int G, int S, int S4, float inv_s) {
@@ -818,11 +814,11 @@ corr_gemm_kernel(const float* __restrict__ zt, float* __restrict__ C,
   __syncthreads();
 
   const int wr = wid >> 1, wc = wid & 1;       // 2x2 wave grid -> 32x32 each
-  f32x4c acc[2][2];
+  f32x4 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4c)(0.f);
+    for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4)(0.f);
 
   const int fr = lane & 15;                     // fragment row/col lane index
   const int kk = lane >> 4;                     // k sub-index 0..3
@@ -932,53 +928,6 @@ f32_to_bf16_kernel(const float* __restrict__ in, uint16_t* __restrict__ out,
     out[i] = f32_to_bf16(in[i]);
 }
 
-// ------------------------------------------------- template instantiations
-#define INSTANTIATE_FWD(WT, HPL)                                              \
-  template __global__ void cbow_fwd_kernel<WT, HPL>(                          \
-      const WT*, const float*, const int*, const int*, const float*,          \
-      long long, float, int, float*, float*, float*, float*, int);
-INSTANTIATE_FWD(float, 1)
-INSTANTIATE_FWD(float, 2)
-INSTANTIATE_FWD(float, 4)
-INSTANTIATE_FWD(float, 8)
-INSTANTIATE_FWD(float, 16)
-INSTANTIATE_FWD(bf16_bits, 1)
-INSTANTIATE_FWD(bf16_bits, 2)
-INSTANTIATE_FWD(bf16_bits, 4)
-INSTANTIATE_FWD(bf16_bits, 8)
-INSTANTIATE_FWD(bf16_bits, 16)
-INSTANTIATE_FWD(fp16_bits, 1)
-INSTANTIATE_FWD(fp16_bits, 2)
-INSTANTIATE_FWD(fp16_bits, 4)
-INSTANTIATE_FWD(fp16_bits, 8)
-INSTANTIATE_FWD(fp16_bits, 16)
-
-#define INSTANTIATE_BWD(HPL)                                                  \
-  template __global__ void cbow_bwd_rows_det_kernel<HPL>(                     \
-      const float*, const int*, const int*, const int*, int, const float*,    \
-      int, float*, const float*);
-INSTANTIATE_BWD(1)
-INSTANTIATE_BWD(2)
-INSTANTIATE_BWD(4)
-INSTANTIATE_BWD(8)
-INSTANTIATE_BWD(16)
-
-#define INSTANTIATE_GEMVR(HPL)                                                \
-  template __global__ void gemv_rows_kernel<HPL>(                             \
-      const float*, const float*, long long, int, float*);
-INSTANTIATE_GEMVR(1)
-INSTANTIATE_GEMVR(2)
-INSTANTIATE_GEMVR(4)
-INSTANTIATE_GEMVR(8)
-INSTANTIATE_GEMVR(16)
-
-#define INSTANTIATE_GEMVC(CPT)                                                \
-  template __global__ void gemv_cols_kernel<CPT>(                             \
-      const float*, const float*, long long, int, float*);
-INSTANTIATE_GEMVC(1)
-INSTANTIATE_GEMVC(2)
-INSTANTIATE_GEMVC(4)
-
 // ======================================================= K9: trunc-normal init
 // Seeded device truncated normal (+-2 sigma, rejection-resampled) — the
 // reference init semantics (tf.truncated_normal, G2Vec.py:234-235)
@@ -1081,23 +1030,13 @@ eval_finish_kernel(const float* __restrict__ piece, const int* __restrict__ offs
     const float* pp = piece + (long long)p * cap;
     for (long long w = w0; w <= w1; ++w) o += pp[w - w0];
     const float y = labels[p];
-    const float corr = (((o > 0.f ? 1.f : 0.f) == y) ? 1.f : 0.f);
+    const float corr = is_correct(o, y);
     if (p < p_split) {
       c0 += corr;
-      if (dO) dO[p] = (1.f / (1.f + expf(-o)) - y) * inv_b;
+      if (dO) dO[p] = dlogit(o, y, inv_b);
     } else {
       c1 += corr;
     }
   }
-  c0 = wave_sum(c0);
-  c1 = wave_sum(c1);
-  __shared__ float sm[8];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wib = threadIdx.x >> 6;
-  if (lane == 0) { sm[wib] = c0; sm[4 + wib] = c1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partials[2 * blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-    partials[2 * blockIdx.x + 1] = sm[4] + sm[5] + sm[6] + sm[7];
-  }
+  block_fold2(c0, c1, partials + 2 * blockIdx.x);
 }

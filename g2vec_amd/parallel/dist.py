@@ -19,6 +19,7 @@ Backend: "nccl" (RCCL on ROCm) when CUDA is available, "gloo" otherwise
 """
 from __future__ import annotations
 
+import atexit
 import datetime
 import os
 from typing import List, Optional, Tuple
@@ -169,6 +170,11 @@ class DistContext:
         return torch.arange(self.rank, n, self.world, device=device)
 
 
+def _destroy_group() -> None:
+    if dist.is_initialized():
+        dist.destroy_process_group()
+
+
 def init_dist(device_hint: str = "auto") -> DistContext:
     """Initialise from torchrun env vars; single-process context otherwise."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -189,6 +195,10 @@ def init_dist(device_hint: str = "auto") -> DistContext:
                    or ("nccl" if use_cuda else "gloo"))
         dist.init_process_group(backend=backend, rank=rank, world_size=world,
                                 timeout=datetime.timedelta(seconds=300))
+        # a rank that exits with the group alive races the backend's worker
+        # threads against interpreter teardown ("terminate called without an
+        # active exception", exit -6, seen on loaded hosts)
+        atexit.register(_destroy_group)
     return DistContext(rank, world, device, world > 1)
 
 

@@ -425,6 +425,82 @@ def test_adam_dense_ragged_vs_fp64(n):
     _assert_adam_close((Wd, md, vd), ref)
 
 
+# The native Adam bindings validate every tensor they dereference. Each bad
+# argument below is OVERSIZED or wrong-typed (never undersized, never host
+# memory): these tests check that the host refuses, and a missing guard
+# would still leave the launch in bounds.
+GUARD_G, GUARD_H = 8, 64
+
+
+def _guard_inputs():
+    t = dict(zip(("W", "m", "v", "c", "who", "mO", "vO"),
+                 _dev(*ke.adam_inputs(GUARD_G, GUARD_H, seed=72))))
+    t["grad"] = torch.outer(t["c"], t["who"]).contiguous()
+    t["lrt"] = torch.tensor([_lr_t()], dtype=torch.float32, device=DEV)
+    return t
+
+
+def _native_adam(fn, t, fused=False):
+    hp = (ADAM_HP["b1"], ADAM_HP["b2"], ADAM_HP["eps"])
+    if fn == "adam_dense":
+        ops.native().adam_dense(t["W"], t["m"], t["v"], t["grad"], t["lrt"],
+                                *hp)
+    else:
+        ops.native().adam_rank1(t["W"], t["m"], t["v"], t["c"], t["who"],
+                                t["lrt"], *hp, mO=t["mO"] if fused else None,
+                                vO=t["vO"] if fused else None)
+
+
+def _bigger(x, shape):
+    return torch.zeros(shape, dtype=x.dtype, device=x.device)
+
+
+ADAM_BAD_ARGS = {
+    "rank1_c_9": ("adam_rank1", False,
+                  lambda t: t.update(c=_bigger(t["c"], GUARD_G + 1))),
+    "rank1_who_128": ("adam_rank1", False,
+                      lambda t: t.update(who=_bigger(t["who"], 2 * GUARD_H))),
+    "rank1_m_9x64": ("adam_rank1", False,
+                     lambda t: t.update(m=_bigger(t["m"],
+                                                  (GUARD_G + 1, GUARD_H)))),
+    "rank1_mO_without_vO": ("adam_rank1", True, lambda t: t.update(vO=None)),
+    "rank1_mO_128": ("adam_rank1", True,
+                     lambda t: t.update(mO=_bigger(t["mO"], 2 * GUARD_H))),
+    "dense_m_numel_plus_1": ("adam_dense", False,
+                             lambda t: t.update(
+                                 m=_bigger(t["m"], GUARD_G * GUARD_H + 1))),
+    "dense_v_f64": ("adam_dense", False,
+                    lambda t: t.update(v=t["v"].double())),
+}
+
+
+@pytest.mark.parametrize("case", sorted(ADAM_BAD_ARGS))
+def test_adam_bindings_reject_bad_arguments(case):
+    """A mis-sized or mis-typed moment / c / who / mO is a RuntimeError from
+    the host, and W, m and v are bitwise unchanged afterwards."""
+    fn, fused, spoil = ADAM_BAD_ARGS[case]
+    t = _guard_inputs()
+    spoil(t)
+    before = {k: t[k].clone() for k in ("W", "m", "v")}
+    with pytest.raises(RuntimeError):
+        _native_adam(fn, t, fused)
+    torch.cuda.synchronize()
+    for k, b in before.items():
+        assert torch.equal(t[k].view(torch.uint8), b.view(torch.uint8)), k
+
+
+@pytest.mark.parametrize("fn,fused", [("adam_rank1", False),
+                                      ("adam_rank1", True),
+                                      ("adam_dense", False)])
+def test_adam_bindings_accept_good_arguments(fn, fused):
+    """The same direct calls with correct 8 x 64 arguments pass the guards
+    and match the fp64 TF1-Adam reference at the Adam tolerances."""
+    t = _guard_inputs()
+    cpu = [t[k].cpu() for k in ("W", "m", "v", "c", "who")]
+    _native_adam(fn, t, fused)
+    _assert_adam_close((t["W"], t["m"], t["v"]), _adam_rank1_ref(*cpu))
+
+
 # ================================================================== PCC
 N_GROUP = 64          # power of two: the 1 / n_group scaling is exact
 
