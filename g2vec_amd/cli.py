@@ -42,8 +42,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pcc-mode", choices=["auto", "edge", "gemm"], default="auto")
     p.add_argument("--pcc-threshold", type=float, default=0.5,
                    help="|PCC| cutoff for graph edges (reference: 0.5)")
-    p.add_argument("--kmeans", choices=["auto", "sklearn", "torch"],
-                   default="auto", help="L-group clustering backend")
+    p.add_argument("--kmeans", choices=["auto", "sklearn", "torch", "hip"],
+                   default="auto",
+                   help="L-group clustering backend (auto = sklearn up to "
+                        "50k genes, torch above; hip = fused HIP Lloyd "
+                        "step on the device-resident embeddings, opt-in)")
+    p.add_argument("--scoring", choices=["host", "device"], default="host",
+                   help="where the d- and t-score vectors are computed "
+                        "(device = row_norms + t_scores kernels; ranking "
+                        "stays on the host)")
     p.add_argument("--activation", choices=["none", "relu"], default="none",
                    help="hidden activation (general chain only; the fast "
                         "path exploits the reference net's linearity)")
@@ -92,7 +99,8 @@ def args_to_config(a: argparse.Namespace) -> G2VecConfig:
         num_biomarker=a.numBiomarker,
         seed=(None if a.seed < 0 else a.seed), dtype=a.dtype, device=a.device,
         pcc_mode=a.pcc_mode, pcc_threshold=a.pcc_threshold,
-        kmeans_backend=a.kmeans, trainer_path=a.trainer_path,
+        kmeans_backend=a.kmeans, scoring_backend=a.scoring,
+        trainer_path=a.trainer_path,
         activation=a.activation, gene_relabel=a.gene_relabel,
         batch_size=a.batch_size, compat_lgroup_bug=a.compat_lgroup_bug,
         early_stop=not a.no_early_stop, earlystop_every=a.earlystop_every,

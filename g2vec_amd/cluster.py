@@ -49,16 +49,160 @@ def kmeans_torch(X, k: int, seed: int = 0, iters: int = 300,
     return assign.cpu().numpy()
 
 
-def find_lgroups(embeddings: np.ndarray, gene_freq: np.ndarray,
+KMEANS_HIP_WIDTHS = (64, 128, 256, 512, 1024)   # the kernels' h = 64 * HPL
+
+
+def _kpp_u01(seed: int, restart: int, draw: int) -> float:
+    """Counter-based uniform in [0, 1) for k-means++ draw `draw` of restart
+    `restart`: its own splitmix64 stream, warmed by one draw like the walk
+    and init streams."""
+    from .ops import cpu_ref
+    with np.errstate(over="ignore"):
+        ctr = np.uint64(restart) * np.uint64(1 << 20) + np.uint64(draw)
+        state = np.uint64(seed) ^ np.uint64(
+            ctr * np.uint64(0x94D049BB133111EB) + np.uint64(1))
+    state, _ = cpu_ref.splitmix64(state)
+    _, r = cpu_ref.splitmix64(state)
+    return float(r >> np.uint64(11)) * (1.0 / 9007199254740992.0)
+
+
+def _kpp_init(X, k: int, seed: int, restart: int):
+    """Seeded k-means++: first centre floor(u*G), then D^2 sampling through
+    kmeans_mind2_ + an f64 cumsum + searchsorted on X's device."""
+    import torch
+
+    from . import ops
+
+    G = X.shape[0]
+    idx = [min(int(_kpp_u01(seed, restart, 0) * G), G - 1)]
+    d2 = torch.full((G,), float("inf"), dtype=torch.float32, device=X.device)
+    for draw in range(1, k):
+        ops.kmeans_mind2_(X, X[idx[-1]], d2)
+        cum = torch.cumsum(d2.double(), 0)
+        total = float(cum[-1])
+        u = _kpp_u01(seed, restart, draw)
+        if total > 0.0:
+            target = torch.tensor([u * total], dtype=torch.float64,
+                                  device=X.device)
+            # right=True: first g with cum[g] > target, so rows at distance
+            # 0 (the centres already chosen) are never drawn
+            g = int(torch.searchsorted(cum, target, right=True))
+        else:
+            g = int(u * G)
+        idx.append(min(g, G - 1))
+    return X[idx].clone()
+
+
+def _lloyd_buffers(X, k: int, max_iter: int):
+    """Out-arguments of kmeans_step shared by every restart: sums, counts,
+    inertia and one n_changed slot per step."""
+    import torch
+    dev = X.device
+    return (torch.empty(k, X.shape[1], dtype=torch.float32, device=dev),
+            torch.empty(k, dtype=torch.int32, device=dev),
+            torch.empty(1, dtype=torch.float64, device=dev),
+            torch.empty(max_iter, dtype=torch.int32, device=dev))
+
+
+def _lloyd(X, C, max_iter: int, check_every: int, bufs):
+    """Step from centroids C (updated in place) until no label changes or
+    max_iter. Step i writes its n_changed into slot i; every check_every
+    steps the new slots come back in one small D2H copy, and the first
+    zero among them is the iteration count. Returns (labels, C, inertia,
+    iterations)."""
+    import torch
+
+    from . import ops
+
+    sums, counts, inertia, changed = bufs
+    labels = torch.full((X.shape[0],), -1, dtype=torch.int32,
+                        device=X.device)
+    it, n_iter = 0, max_iter
+    while it < max_iter:
+        hi = min(it + check_every, max_iter)
+        for i in range(it, hi):
+            ops.kmeans_step(X, C, labels, labels, C, sums, counts,
+                            changed[i:i + 1], inertia)
+        zero = (changed[it:hi] == 0).nonzero().flatten().cpu()
+        if zero.numel():
+            n_iter = it + int(zero[0]) + 1
+            break
+        it = hi
+    return labels, C, float(inertia[0]), n_iter
+
+
+def kmeans_hip(X, k: int, seed: int = 0, n_init: int = 10,
+               max_iter: int = 300, check_every: int = 4):
+    """Seeded Lloyd k-means on the fused kmeans_step op: HIP kernels for a
+    CUDA tensor, their CPU mirror for a CPU tensor. X: f32 [G, h] tensor.
+
+    Each of the n_init restarts starts from a seeded k-means++ draw and
+    steps until no label changes (or max_iter). n_changed is read back once
+    every check_every steps — one small D2H per read, no per-step sync.
+    A step with n_changed == 0 is a fixed point of a deterministic step
+    (same labels -> same means -> same labels), so the steps run past it
+    change nothing and the result is bitwise independent of check_every.
+    The restart with the lowest inertia wins, ties to the lowest index.
+
+    Returns (labels i32[G] tensor on X's device, centroids f32[k, h],
+    inertia float, iterations int) of the winning restart; iterations
+    counts the steps up to and including the first one without a change."""
+    import torch
+
+    if not (1 <= k <= 8):
+        raise ValueError(f"kmeans_hip: k must be in [1, 8], got {k}")
+    if n_init < 1 or max_iter < 1 or check_every < 1:
+        raise ValueError("kmeans_hip: n_init, max_iter and check_every "
+                         "must be >= 1")
+    X = X.float().contiguous()
+    G, h = X.shape
+    if G < 1:
+        raise ValueError("kmeans_hip: X has no rows")
+    if h not in KMEANS_HIP_WIDTHS:
+        # zero columns add (0 - 0)^2 = 0 to every distance: pad up to the
+        # next kernel width (exact), trim the centroids on the way out
+        wide = [w for w in KMEANS_HIP_WIDTHS if w >= h]
+        if not wide:
+            raise ValueError(f"kmeans_hip: h={h} exceeds "
+                             f"{KMEANS_HIP_WIDTHS[-1]} columns")
+        Xp = torch.zeros(G, wide[0], dtype=torch.float32, device=X.device)
+        Xp[:, :h] = X
+        X = Xp
+    bufs = _lloyd_buffers(X, k, max_iter)
+    best = None
+    for restart in range(n_init):
+        labels, C, val, n_iter = _lloyd(X, _kpp_init(X, k, seed, restart),
+                                        max_iter, check_every, bufs)
+        if best is None or val < best[2]:
+            best = (labels, C[:, :h].contiguous(), val, n_iter)
+    return best
+
+
+def find_lgroups(embeddings, gene_freq: np.ndarray,
                  compat_lgroup_bug: bool = False, backend: str = "auto",
-                 device=None) -> np.ndarray:
+                 device=None, info=None) -> np.ndarray:
     """embeddings: f32 [G, h]; gene_freq: int [G] in {0 good,1 poor,2 other}.
     Returns int32 [G] with 0 good / 1 poor / 2 other.
     backend: 'sklearn' (reference parity: KMeans random_state=0) |
-    'torch' (scalable, GPU-capable) | 'auto' (sklearn up to 50k genes)."""
+    'torch' (scalable, GPU-capable) | 'hip' (kmeans_hip: fused HIP Lloyd
+    step; embeddings may be a torch tensor already on its device, which is
+    then used in place) | 'auto' (sklearn up to 50k genes, torch above).
+    info: optional dict; the hip backend records kmeans_inertia and
+    kmeans_iterations in it."""
     if backend == "auto":
         backend = "sklearn" if embeddings.shape[0] <= 50_000 else "torch"
-    if backend == "torch":
+    if backend == "hip":
+        import torch
+        X = embeddings
+        if not torch.is_tensor(X):
+            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+            if device is not None:
+                X = X.to(device)
+        labels, _c, inertia, n_iter = kmeans_hip(X, 3, seed=0)
+        km_idx = labels.cpu().numpy()
+        if info is not None:
+            info.update(kmeans_inertia=inertia, kmeans_iterations=n_iter)
+    elif backend == "torch":
         import torch
         X = torch.from_numpy(np.ascontiguousarray(embeddings))
         if device is not None:

@@ -40,6 +40,12 @@ class G2VecConfig:
     pcc_threshold: float = 0.5      # |PCC| cutoff (G2Vec.py:385-390)
     pcc_mode: str = "auto"          # "edge" (per-edge dot) | "gemm" (MFMA corr GEMM) | "auto"
     kmeans_backend: str = "auto"    # "sklearn" (reference parity) | "torch" (scales) | "auto"
+                                    # | "hip" (opt-in: fused HIP Lloyd step on
+                                    # the device-resident W_ih, cluster.kmeans_hip)
+    scoring_backend: str = "host"   # "host" (NumPy d/t-scores) | "device"
+                                    # (opt-in: row_norms + t_scores kernels
+                                    # produce the two [G] vectors; min-max,
+                                    # sort and top-N stay on the host)
     compat_lgroup_bug: bool = False  # reproduce the shipped G2Vec.py:186-194 behaviour
     early_stop: bool = True
     earlystop_every: int = 1        # early-stop accuracy readback granularity:
@@ -121,8 +127,10 @@ class G2VecConfig:
                 "activation != none requires --trainer-path general: the "
                 "fast path exploits the reference net's LINEARITY "
                 "(o = sum s_g), which a hidden activation breaks")
-        if self.kmeans_backend not in ("auto", "sklearn", "torch"):
+        if self.kmeans_backend not in ("auto", "sklearn", "torch", "hip"):
             raise ValueError(f"bad kmeans_backend {self.kmeans_backend}")
+        if self.scoring_backend not in ("host", "device"):
+            raise ValueError(f"bad scoring_backend {self.scoring_backend}")
         if self.gene_relabel not in ("auto", "on", "off"):
             raise ValueError(f"bad gene_relabel {self.gene_relabel}")
 

@@ -293,3 +293,49 @@ def corr_gemm(zt, n_group: int):
     if zt.is_cuda:
         return native().corr_gemm(zt, int(n_group))
     return cpu_ref.corr_gemm(zt, n_group)
+
+
+# ------------------------------------------------------------------ steps 5-6: k-means / scoring
+def kmeans_step(X, C, prev, labels, C_new, sums, counts, n_changed,
+                inertia) -> None:
+    """One fused Lloyd iteration over X f32[G, h] with centroids C f32[k, h]
+    (k <= 8), everything through out-arguments: labels i32[G] (argmin of the
+    direct squared distances, lowest index on ties), sums f32[k, h],
+    counts i32[k], n_changed i32[1] (rows whose label differs from prev),
+    inertia f64[1] and C_new = sums / float(counts) (an empty cluster keeps
+    its row). prev may be labels and C_new may be C. On GPU h must be one
+    of 64/128/256/512/1024."""
+    if X.is_cuda:
+        native().kmeans_step(X, C, prev, labels, C_new, sums, counts,
+                             n_changed, inertia)
+        return
+    cpu_ref.kmeans_step(X, C, prev, labels, C_new, sums, counts, n_changed,
+                        inertia)
+
+
+def kmeans_mind2_(X, c, d2) -> None:
+    """d2[g] = min(d2[g], |x_g - c|^2) for one new centre c f32[h]."""
+    if X.is_cuda:
+        native().kmeans_mind2_(X, c, d2)
+        return
+    cpu_ref.kmeans_mind2_(X, c, d2)
+
+
+def row_norms(W) -> torch.Tensor:
+    """d-score: f32[G] row L2 norms of W f32[G, h], f64-accumulated."""
+    if W.is_cuda:
+        out = torch.empty(W.shape[0], dtype=torch.float32, device=W.device)
+        native().row_norms_(W, out)
+        return out
+    return cpu_ref.row_norms(W)
+
+
+def t_scores(expr, labels) -> torch.Tensor:
+    """t-score: f32[G] |pooled t| per gene column of expr f32[S, G]
+    (samples x genes), labels i32/i64[S] with 0 good / 1 poor."""
+    if expr.is_cuda:
+        out = torch.empty(expr.shape[1], dtype=torch.float32,
+                          device=expr.device)
+        native().t_scores_(expr, labels, out)
+        return out
+    return cpu_ref.t_scores(expr, labels)

@@ -252,3 +252,71 @@ def pcc_edges(zt: torch.Tensor, edge_idx: torch.Tensor, n_group: int) -> torch.T
 def corr_gemm(zt: torch.Tensor, n_group: int) -> torch.Tensor:
     """Full correlation matrix C = Zt Zt^T / S (the MFMA GEMM path on GPU)."""
     return (zt @ zt.t()) / n_group
+
+
+# ------------------------------------------------------------------ steps 5-6: k-means / scoring
+def _dist2_to(X: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """|x_g - c|^2 per row as the direct fp32 sum of squared differences
+    (never the |x|^2 - 2xc + |c|^2 expansion), like row_dist2 on the GPU."""
+    d = X - c
+    return (d * d).sum(dim=1)
+
+
+def kmeans_step(X, C, prev, labels, C_new, sums, counts, n_changed,
+                inertia) -> None:
+    """Mirror of kmeans_step_kernel + kmeans_fold_kernel, same
+    out-arguments. Ties go to the lowest cluster index (strict <), an
+    empty cluster keeps its old centroid row, C' = sums / float(counts) in
+    fp32, inertia = f64 sum of the winning fp32 distances. prev may be
+    labels and C_new may be C."""
+    k = C.shape[0]
+    best = _dist2_to(X, C[0])
+    lab = torch.zeros(X.shape[0], dtype=torch.int64)
+    for j in range(1, k):
+        dj = _dist2_to(X, C[j])
+        better = dj < best
+        best = torch.where(better, dj, best)
+        lab[better] = j
+    n_changed[0] = int((lab != prev.long()).sum())
+    inertia[0] = best.double().sum()
+    s = torch.zeros(k, X.shape[1], dtype=torch.float32).index_add_(0, lab, X)
+    cnt = torch.bincount(lab, minlength=k)
+    new = torch.where((cnt > 0)[:, None],
+                      s / cnt.clamp(min=1).float()[:, None], C)
+    labels.copy_(lab.int())
+    sums.copy_(s.view_as(sums))
+    counts.copy_(cnt.int())
+    C_new.copy_(new)
+
+
+def kmeans_mind2_(X, c, d2) -> None:
+    """d2[g] = min(d2[g], |x_g - c|^2) for one new centre (k-means++)."""
+    torch.minimum(d2, _dist2_to(X, c.view(-1)), out=d2)
+
+
+def row_norms(W: torch.Tensor) -> torch.Tensor:
+    """d-score: row L2 norms accumulated in f64, rounded to fp32 once."""
+    Wd = W.double()
+    return (Wd * Wd).sum(dim=1).sqrt().float()
+
+
+def t_scores(expr: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """|pooled-variance t| per gene column of expr[S, G], label 0 vs 1, in
+    f64 with two passes (means, then squared deviations): the formula of
+    scoring.t_scores and the rules of t_scores_kernel (0 when d1 <= 0 or a
+    group has fewer than 2 samples)."""
+    G = expr.shape[1]
+    x = expr[labels == 0].double()
+    y = expr[labels == 1].double()
+    nx, ny = x.shape[0], y.shape[0]
+    if nx < 2 or ny < 2:
+        return torch.zeros(G, dtype=torch.float32)
+    mx, my = x.sum(dim=0) / nx, y.sum(dim=0) / ny
+    sx = (((x - mx) ** 2).sum(dim=0) / (nx - 1.0)).sqrt()
+    sy = (((y - my) ** 2).sum(dim=0) / (ny - 1.0)).sqrt()
+    d1 = (((nx - 1.0) * sx * sx + (ny - 1.0) * sy * sy)
+          / (nx + ny - 2.0)).sqrt()
+    d2 = (1.0 / nx + 1.0 / ny) ** 0.5
+    pos = d1 > 0.0
+    t = torch.where(pos, (mx - my) / torch.where(pos, d1, 1.0) / d2, 0.0)
+    return t.abs().float()

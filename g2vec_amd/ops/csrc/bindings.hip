@@ -534,6 +534,150 @@ torch::Tensor bf16_copy(torch::Tensor src) {
   return out;
 }
 
+// ------------------------------------------- steps 5-6: k-means and scoring
+inline void check_f64(const torch::Tensor& t, const char* name) {
+  check_gpu_cont(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kDouble, name, " must be float64");
+}
+#define CHECK_F64(x) check_f64((x), #x)
+
+// the row-tile kernels move rows as 16-byte pieces
+inline void check_rows16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+#define CHECK_ROWS16(x) check_rows16((x), #x)
+
+// kmeans_step LDS budget: k*h centroid floats + one [k][h] accumulator per
+// wave (4 waves) = 5*k*h floats of the CU's 160 KiB
+constexpr long long KM_LDS_LIMIT = 160 * 1024;
+
+void kmeans_step(torch::Tensor X, torch::Tensor C, torch::Tensor prev,
+                 torch::Tensor labels, torch::Tensor C_new,
+                 torch::Tensor sums, torch::Tensor counts,
+                 torch::Tensor n_changed, torch::Tensor inertia) {
+  // one fused Lloyd iteration, all outputs through out-arguments; prev may
+  // be labels and C_new may be C (see the kernels)
+  CHECK_F32(X); CHECK_F32(C); CHECK_I32(prev); CHECK_I32(labels);
+  CHECK_F32(C_new); CHECK_F32(sums); CHECK_I32(counts); CHECK_I32(n_changed);
+  CHECK_F64(inertia);
+  TORCH_CHECK(X.dim() == 2 && C.dim() == 2, "X must be [G, h] and C [k, h]");
+  const long long G = X.size(0);
+  const int h = (int)X.size(1);
+  const int hpl = hpl_for(h);
+  const long long k = C.size(0);
+  TORCH_CHECK(C.size(1) == h, "C must have X's ", h, " columns");
+  TORCH_CHECK(k >= 1 && k <= KM_MAX_K, "k must be in [1, ", KM_MAX_K,
+              "], got ", k);
+  const long long lds = 5 * k * h * (long long)sizeof(float);
+  TORCH_CHECK(lds <= KM_LDS_LIMIT, "kmeans_step: k*h = ", k * h,
+              " needs ", lds, " B of LDS (centroids + 4 per-wave "
+              "accumulators), over the ", KM_LDS_LIMIT, " B budget");
+  TORCH_CHECK(G >= 1, "X must have at least one row");
+  CHECK_ROWS16(X);
+  TORCH_CHECK(prev.numel() == G && labels.numel() == G,
+              "prev and labels must have one element per X row");
+  TORCH_CHECK(C_new.dim() == 2 && C_new.size(0) == k && C_new.size(1) == h,
+              "C_new must have C's shape");
+  TORCH_CHECK(sums.numel() == k * h, "sums must be [k, h]");
+  TORCH_CHECK(counts.numel() == k, "counts must have k elements");
+  TORCH_CHECK(n_changed.numel() == 1 && inertia.numel() == 1,
+              "n_changed and inertia must have one element");
+  // >= 16 rows per block amortize the LDS clear and the partial write; the
+  // cap is what the chip holds at once (blocks per CU by LDS, at most the 8
+  // that 32 waves allow): more blocks would queue behind the resident ones
+  // and only lengthen the partial table ([grid, k*h]) and the fold
+  int n_cu = 0, dev = 0;
+  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
+                  hipDeviceGetAttribute(&n_cu,
+                                        hipDeviceAttributeMultiprocessorCount,
+                                        dev) == hipSuccess && n_cu >= 1,
+              "kmeans_step: cannot read the device's CU count");
+  long long per_cu = KM_LDS_LIMIT / lds;
+  if (per_cu > 8) per_cu = 8;
+  int grid = grid_for(G, 16);
+  if (grid > n_cu * per_cu) grid = (int)(n_cu * per_cu);
+  auto psums = torch::empty({grid, k * h}, opts_on(X));
+  auto pcnt = torch::empty({grid, KM_PCNT}, opts_on(X, at::kInt));
+  auto pinert = torch::empty({grid}, opts_on(X, at::kDouble));
+  dispatch_hpl(hpl, [&](auto HPL) {
+    hipLaunchKernelGGL((kmeans_step_kernel<decltype(HPL)::value>), dim3(grid),
+                       dim3(256), (size_t)lds, cur_stream(),
+                       X.data_ptr<float>(), C.data_ptr<float>(),
+                       prev.data_ptr<int>(), labels.data_ptr<int>(), G, h,
+                       (int)k, psums.data_ptr<float>(), pcnt.data_ptr<int>(),
+                       pinert.data_ptr<double>());
+    LAUNCH_CHECK();
+  });
+  hipLaunchKernelGGL(kmeans_fold_kernel, dim3(grid_for(k * h, 4)), dim3(256),
+                     0, cur_stream(), psums.data_ptr<float>(),
+                     pcnt.data_ptr<int>(), pinert.data_ptr<double>(), grid,
+                     (int)k, h, C.data_ptr<float>(), C_new.data_ptr<float>(),
+                     sums.data_ptr<float>(), counts.data_ptr<int>(),
+                     n_changed.data_ptr<int>(), inertia.data_ptr<double>());
+  LAUNCH_CHECK();
+}
+
+void kmeans_mind2_(torch::Tensor X, torch::Tensor c, torch::Tensor d2) {
+  CHECK_F32(X); CHECK_F32(c); CHECK_F32(d2);
+  TORCH_CHECK(X.dim() == 2, "X must be [G, h]");
+  const long long G = X.size(0);
+  const int h = (int)X.size(1);
+  const int hpl = hpl_for(h);
+  TORCH_CHECK(c.numel() == h, "c must have one element per X column");
+  TORCH_CHECK(d2.numel() == G, "d2 must have one element per X row");
+  CHECK_ROWS16(X); CHECK_ROWS16(c);
+  if (G == 0) return;
+  int grid = grid_for(G, 4);
+  if (grid > 8192) grid = 8192;
+  dispatch_hpl(hpl, [&](auto HPL) {
+    hipLaunchKernelGGL((kmeans_mind2_kernel<decltype(HPL)::value>),
+                       dim3(grid), dim3(256), 0, cur_stream(),
+                       X.data_ptr<float>(), c.data_ptr<float>(), G, h,
+                       d2.data_ptr<float>());
+    LAUNCH_CHECK();
+  });
+}
+
+void row_norms_(torch::Tensor W, torch::Tensor out) {
+  CHECK_F32(W); CHECK_F32(out);
+  TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
+  const long long G = W.size(0);
+  const int h = (int)W.size(1);
+  const int hpl = hpl_for(h);
+  TORCH_CHECK(out.numel() == G, "out must have one element per W row");
+  CHECK_ROWS16(W);
+  if (G == 0) return;
+  int grid = grid_for(G, 4);
+  if (grid > 8192) grid = 8192;
+  dispatch_hpl(hpl, [&](auto HPL) {
+    hipLaunchKernelGGL((row_norms_kernel<decltype(HPL)::value>), dim3(grid),
+                       dim3(256), 0, cur_stream(), W.data_ptr<float>(), G, h,
+                       out.data_ptr<float>());
+    LAUNCH_CHECK();
+  });
+}
+
+void t_scores_(torch::Tensor expr, torch::Tensor labels, torch::Tensor out) {
+  // labels: i32 or i64 [S]; the kernel reads an i32 copy
+  CHECK_F32(expr); CHECK_GPU_CONT(labels); CHECK_F32(out);
+  TORCH_CHECK(labels.scalar_type() == at::kInt ||
+                  labels.scalar_type() == at::kLong,
+              "labels must be int32 or int64");
+  TORCH_CHECK(expr.dim() == 2, "expr must be [S, G]");
+  const long long S = expr.size(0);
+  const long long G = expr.size(1);
+  TORCH_CHECK(S >= 1 && S < (1LL << 31), "expr needs 1 <= S < 2^31 rows");
+  TORCH_CHECK(labels.numel() == S, "labels must have one element per sample");
+  TORCH_CHECK(out.numel() == G, "out must have one element per gene");
+  if (G == 0) return;
+  auto lab = labels.to(at::kInt).contiguous();
+  hipLaunchKernelGGL(t_scores_kernel, dim3(grid_for(G, 256)), dim3(256), 0,
+                     cur_stream(), expr.data_ptr<float>(), lab.data_ptr<int>(),
+                     (int)S, G, out.data_ptr<float>());
+  LAUNCH_CHECK();
+}
+
 // ------------------------------------------------- native host TSV parser
 std::tuple<std::vector<std::string>, std::vector<std::string>, torch::Tensor>
 parse_expression_tsv(const std::string& path) {
@@ -647,6 +791,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_rows_", &gemv_rows_, "s = W @ x (wave-per-row GEMV, out-arg)");
   m.def("gemv_cols_", &gemv_cols_, "out = W^T c (partials + fold, out-arg)");
   m.def("bf16_copy", &bf16_copy, "f32 -> bf16 cast kernel");
+  m.def("kmeans_step", &kmeans_step,
+        py::arg("X"), py::arg("C"), py::arg("prev"), py::arg("labels"),
+        py::arg("C_new"), py::arg("sums"), py::arg("counts"),
+        py::arg("n_changed"), py::arg("inertia"),
+        "one fused Lloyd iteration (assign + sums/counts/inertia + C')");
+  m.def("kmeans_mind2_", &kmeans_mind2_,
+        "d2 = min(d2, |x - c|^2) for one new centre (k-means++)");
+  m.def("row_norms_", &row_norms_, "row L2 norms, f64-accumulated (out-arg)");
+  m.def("t_scores_", &t_scores_, "|pooled t| per gene column (out-arg)");
   m.def("parse_expression_tsv", &parse_expression_tsv,
         "native expression TSV parser");
 }

@@ -23,6 +23,11 @@
 //   trunc_normal_kernel         (K9) seeded +-2 sigma truncated-normal fill
 //   eval_scan_kernel            instance-parallel eval: segmented scan to per-window piece sums
 //   eval_finish_kernel          thread-per-path fold of the pieces, counts + train dlogits
+//   kmeans_step_kernel<HPL>     (step 5) fused Lloyd iteration: assign + per-block sums/counts/inertia
+//   kmeans_fold_kernel          folds those partials, writes sums/counts/n_changed/inertia and C'
+//   kmeans_mind2_kernel<HPL>    (step 5) k-means++ support: d2 = min(d2, |x - c|^2)
+//   row_norms_kernel<HPL>       (step 6) d-score: f64-accumulated row L2 norms
+//   t_scores_kernel             (step 6) |pooled t| per gene column, f64 two-pass
 //
 // The templates are instantiated by their launch sites in bindings.hip, the
 // one translation unit that includes this file.
@@ -75,7 +80,10 @@ __device__ __forceinline__ float unif(float v) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// T: float everywhere on the training path; int / double in the k-means
+// folds (counts, f64 inertia). One shuffle tree for all of them.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
   for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
   return __shfl(v, 0);
 }
@@ -1039,4 +1047,316 @@ eval_finish_kernel(const float* __restrict__ piece, const int* __restrict__ offs
     }
   }
   block_fold2(c0, c1, partials + 2 * blockIdx.x);
+}
+
+// ==================================== steps 5-6: L-group k-means and scoring
+// Row tile of the wave-per-row kernels below: a lane owns HPL = h/64
+// columns as NCH chunks of VEC <= 4 floats, chunk c at column
+// (c*64 + lane)*VEC. Every wave instruction then reads 64 consecutive
+// 4..16-byte pieces: a fully coalesced global load, and a conflict-free
+// ds_read when the row lives in LDS (lane*64 B strides would put four lanes
+// of each ds_read_b128 lane group on one bank). Rows must be 16-byte
+// aligned (the bindings check the base; h is a multiple of 64): the
+// alignment promise is what lets LDS rows move as ds_read/write_b128.
+template <int HPL>
+__device__ __forceinline__ void row_load(const float* row, int lane,
+                                         float (&x)[HPL]) {
+  constexpr int VEC = HPL < 4 ? HPL : 4;
+  row = (const float*)__builtin_assume_aligned(row, VEC * sizeof(float));
+#pragma unroll
+  for (int c = 0; c < HPL / VEC; ++c)
+    __builtin_memcpy(&x[c * VEC], row + (c * WAVE + lane) * VEC,
+                     VEC * sizeof(float));
+}
+
+template <int HPL>
+__device__ __forceinline__ void row_store(float* row, int lane,
+                                          const float (&x)[HPL]) {
+  constexpr int VEC = HPL < 4 ? HPL : 4;
+  row = (float*)__builtin_assume_aligned(row, VEC * sizeof(float));
+#pragma unroll
+  for (int c = 0; c < HPL / VEC; ++c)
+    __builtin_memcpy(row + (c * WAVE + lane) * VEC, &x[c * VEC],
+                     VEC * sizeof(float));
+}
+
+// |x - c|^2 as the direct sum of squared differences (no |x|^2 - 2xc + |c|^2
+// expansion: dyadic inputs stay exact and nothing cancels)
+template <int HPL>
+__device__ __forceinline__ float row_dist2(const float (&x)[HPL],
+                                           const float (&c)[HPL]) {
+  float p = 0.f;
+#pragma unroll
+  for (int i = 0; i < HPL; ++i) {
+    const float d = x[i] - c[i];
+    p += d * d;
+  }
+  return wave_sum(p);
+}
+
+#define KM_MAX_K 8
+#define KM_PCNT (KM_MAX_K + 1)     // per-block ints: counts[8], n_changed
+
+// One fused Lloyd iteration. One wave per row (two adjacent rows per pass),
+// grid-strided. Dynamic LDS,
+// 5*k*h floats: the k centroids (block-resident) and one [k][h] sum
+// accumulator PER WAVE. A row's label is wave-uniform, so the wave adds the
+// row into its own accumulator's label row with plain LDS read-add-write:
+// no atomics, and X is read once for assign + update. Counts, n_changed and
+// the f64 inertia ride in wave-uniform registers. Epilogue: the 4 waves'
+// accumulators are summed in ascending wave order into this block's
+// partial; kmeans_fold_kernel folds the blocks. Every order is fixed by
+// (G, grid), so a step is bitwise reproducible.
+// prev/labels may alias (a row's wave reads prev[g] before writing
+// labels[g]); neither is __restrict__.
+template <int HPL>
+__global__ void __launch_bounds__(256)
+kmeans_step_kernel(const float* __restrict__ X, const float* __restrict__ C,
+                   const int* prev, int* labels, long long G, int h, int k,
+                   float* __restrict__ psums, int* __restrict__ pcnt,
+                   double* __restrict__ pinert) {
+  extern __shared__ __attribute__((aligned(16))) float km_lds[];
+  const int kh = k * h;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = uni(threadIdx.x >> 6);
+  const int wpb = blockDim.x >> 6;             // 4: the epilogue assumes it
+  float* cen = km_lds;                         // [k][h]
+  float* acc = km_lds + (1 + wib) * kh;        // this wave's [k][h]
+  for (int i = threadIdx.x; i < kh; i += blockDim.x) cen[i] = C[i];
+  for (int i = threadIdx.x; i < wpb * kh; i += blockDim.x)
+    km_lds[kh + i] = 0.f;
+  __syncthreads();
+
+  int cnt[KM_MAX_K];
+#pragma unroll
+  for (int j = 0; j < KM_MAX_K; ++j) cnt[j] = 0;
+  int changed = 0;
+  double inert = 0.0;
+  // two adjacent rows per wave and pass: both loads are in flight together
+  // and the two rows' reduction chains interleave (one row per pass ran at
+  // the latency of load + k shuffle trees, well under the HBM rate)
+  for (long long g = ((long long)blockIdx.x * wpb + wib) * 2; g < G;
+       g += (long long)gridDim.x * wpb * 2) {
+    const bool two = g + 1 < G;                // wave-uniform
+    float xa[HPL], xb[HPL], cv[HPL];
+    row_load<HPL>(X + g * (long long)h, lane, xa);
+    row_load<HPL>(X + (two ? g + 1 : g) * (long long)h, lane, xb);
+    float besta = 0.f, bestb = 0.f;
+    int ja = 0, jb = 0;
+    for (int j = 0; j < k; ++j) {
+      row_load<HPL>(cen + j * h, lane, cv);
+      const float da = row_dist2<HPL>(xa, cv);
+      const float db = row_dist2<HPL>(xb, cv);
+      if (j == 0 || da < besta) { besta = da; ja = j; }  // ties: lowest index
+      if (j == 0 || db < bestb) { bestb = db; jb = j; }
+    }
+    ja = uni(ja);
+    jb = uni(jb);
+    G2V_ASSERT(ja >= 0 && ja < k && jb >= 0 && jb < k);
+    float* arow = acc + ja * h;
+    row_load<HPL>(arow, lane, cv);
+#pragma unroll
+    for (int i = 0; i < HPL; ++i) cv[i] += xa[i];
+    row_store<HPL>(arow, lane, cv);
+#pragma unroll
+    for (int j = 0; j < KM_MAX_K; ++j) cnt[j] += (ja == j) ? 1 : 0;
+    changed += (prev[g] != ja) ? 1 : 0;
+    inert += (double)besta;
+    if (lane == 0) labels[g] = ja;
+    if (two) {                                 // row g + 1, after row g
+      arow = acc + jb * h;
+      row_load<HPL>(arow, lane, cv);
+#pragma unroll
+      for (int i = 0; i < HPL; ++i) cv[i] += xb[i];
+      row_store<HPL>(arow, lane, cv);
+#pragma unroll
+      for (int j = 0; j < KM_MAX_K; ++j) cnt[j] += (jb == j) ? 1 : 0;
+      changed += (prev[g + 1] != jb) ? 1 : 0;
+      inert += (double)bestb;
+      if (lane == 0) labels[g + 1] = jb;
+    }
+  }
+  __syncthreads();                             // all rows in, cen[] is dead
+
+  float* ps = psums + (long long)blockIdx.x * kh;
+  for (int i = threadIdx.x; i < kh; i += blockDim.x) {
+    const float* a = km_lds + kh + i;
+    ps[i] = ((a[0] + a[kh]) + a[2 * kh]) + a[3 * kh];
+  }
+  // the wave scalars go through the dead centroid region (kh >= 64 floats;
+  // 4 doubles + 4*9 ints = 44): the block may own all 160 KiB of LDS as
+  // dynamic memory (k*h = 8192), which leaves no room for a static array
+  double* sd = (double*)cen;                   // [4]
+  int* si = (int*)cen + 2 * 4;                 // [4][KM_PCNT]
+  if (lane == 0) {
+    sd[wib] = inert;
+#pragma unroll
+    for (int j = 0; j < KM_MAX_K; ++j) si[wib * KM_PCNT + j] = cnt[j];
+    si[wib * KM_PCNT + KM_MAX_K] = changed;
+  }
+  __syncthreads();
+  if (threadIdx.x < KM_PCNT) {
+    const int j = threadIdx.x;
+    pcnt[(long long)blockIdx.x * KM_PCNT + j] =
+        si[j] + si[KM_PCNT + j] + si[2 * KM_PCNT + j] + si[3 * KM_PCNT + j];
+  }
+  if (threadIdx.x == KM_PCNT)
+    pinert[blockIdx.x] = ((sd[0] + sd[1]) + sd[2]) + sd[3];
+}
+
+// Folds the per-block partials of kmeans_step_kernel. One wave per sums
+// element, like fold_cols_kernel: lane l takes blocks l, l+64, ... in
+// ascending order, then the fixed shuffle tree. The element's wave also
+// folds its cluster's count and writes C' = sum / float(count) in fp32 (an
+// empty cluster keeps its old row); wave 0 folds n_changed and the f64
+// inertia. C_new may alias C_old: element e is read and written by the same
+// lane.
+extern "C" __global__ void __launch_bounds__(256)
+kmeans_fold_kernel(const float* __restrict__ psums,
+                   const int* __restrict__ pcnt,
+                   const double* __restrict__ pinert, int n_blocks, int k,
+                   int h, const float* C_old, float* C_new,
+                   float* __restrict__ sums, int* __restrict__ counts,
+                   int* __restrict__ n_changed, double* __restrict__ inertia) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wpb = blockDim.x >> 6;
+  const int kh = k * h;
+  for (int e = blockIdx.x * wpb + (threadIdx.x >> 6); e < kh;
+       e += gridDim.x * wpb) {
+    const int j = e / h;
+    float s = 0.f;
+    int c = 0;
+    for (int b = lane; b < n_blocks; b += WAVE) {
+      s += psums[(long long)b * kh + e];
+      c += pcnt[(long long)b * KM_PCNT + j];
+    }
+    s = wave_sum(s);
+    c = wave_sum(c);
+    if (lane == 0) {
+      sums[e] = s;
+      C_new[e] = (c > 0) ? s / (float)c : C_old[e];
+      if (e == j * h) counts[j] = c;
+    }
+    if (e == 0) {
+      int ch = 0;
+      double in = 0.0;
+      for (int b = lane; b < n_blocks; b += WAVE) {
+        ch += pcnt[(long long)b * KM_PCNT + KM_MAX_K];
+        in += pinert[b];
+      }
+      ch = wave_sum(ch);
+      in = wave_sum(in);
+      if (lane == 0) { n_changed[0] = ch; inertia[0] = in; }
+    }
+  }
+}
+
+// k-means++ D^2 sampling support: d2[g] = min(d2[g], |x_g - c|^2) for one
+// new centre c[h] (same row tile and distance as kmeans_step_kernel).
+template <int HPL>
+__global__ void __launch_bounds__(256)
+kmeans_mind2_kernel(const float* __restrict__ X, const float* __restrict__ c,
+                    long long G, int h, float* __restrict__ d2) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  float cv[HPL];
+  row_load<HPL>(c, lane, cv);
+  for (long long g = (long long)blockIdx.x * wpb + wib; g < G;
+       g += (long long)gridDim.x * wpb) {
+    float x[HPL];
+    row_load<HPL>(X + g * (long long)h, lane, x);
+    const float d = row_dist2<HPL>(x, cv);
+    if (lane == 0) d2[g] = fminf(d2[g], d);
+  }
+}
+
+// d-score: out[g] = sqrt(sum_j W[g, j]^2), accumulated in f64 and rounded
+// to fp32 once.
+template <int HPL>
+__global__ void __launch_bounds__(256)
+row_norms_kernel(const float* __restrict__ W, long long G, int h,
+                 float* __restrict__ out) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  for (long long g = (long long)blockIdx.x * wpb + wib; g < G;
+       g += (long long)gridDim.x * wpb) {
+    float x[HPL];
+    row_load<HPL>(W + g * (long long)h, lane, x);
+    double p = 0.0;
+#pragma unroll
+    for (int i = 0; i < HPL; ++i) p += (double)x[i] * (double)x[i];
+    p = wave_sum(p);
+    if (lane == 0) out[g] = (float)sqrt(p);
+  }
+}
+
+// t-score: |pooled-variance two-sample t| per gene column of expr[S, G]
+// (row-major, samples x genes), label 0 (good) vs 1 (poor); other labels
+// are left out. One THREAD per gene, so each sample row is a coalesced read
+// across genes. Two passes over the column in f64: group means, then the
+// sums of squared deviations; then the formula of scoring.t_scores. 0 when
+// d1 <= 0 or a group has fewer than 2 samples. Sample labels are staged in
+// LDS tile by tile (any S) and read as broadcasts.
+#define TS_TILE 1024
+
+extern "C" __global__ void __launch_bounds__(256)
+t_scores_kernel(const float* __restrict__ expr, const int* __restrict__ labels,
+                int S, long long G, float* __restrict__ out) {
+  __shared__ int lab[TS_TILE];
+  for (long long g0 = (long long)blockIdx.x * blockDim.x; g0 < G;
+       g0 += (long long)gridDim.x * blockDim.x) {
+    const long long g = g0 + threadIdx.x;
+    const bool act = g < G;
+    int n0 = 0, n1 = 0;
+    double m0 = 0.0, m1 = 0.0, q0 = 0.0, q1 = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+      double a0 = 0.0, a1 = 0.0;
+      for (int t0 = 0; t0 < S; t0 += TS_TILE) {
+        const int nt = (S - t0 < TS_TILE) ? S - t0 : TS_TILE;
+        __syncthreads();                       // readers of the last tile done
+        for (int i = threadIdx.x; i < nt; i += blockDim.x)
+          lab[i] = labels[t0 + i];
+        __syncthreads();
+        if (act) {
+          const float* col = expr + (long long)t0 * G + g;
+#pragma unroll 4
+          for (int i = 0; i < nt; ++i) {
+            const int l = lab[i];
+            const double v = (double)col[(long long)i * G];
+            if (pass == 0) {
+              a0 += (l == 0) ? v : 0.0;
+              a1 += (l == 1) ? v : 0.0;
+              n0 += (l == 0) ? 1 : 0;
+              n1 += (l == 1) ? 1 : 0;
+            } else {
+              const double d0 = v - m0, d1 = v - m1;
+              a0 += (l == 0) ? d0 * d0 : 0.0;
+              a1 += (l == 1) ? d1 * d1 : 0.0;
+            }
+          }
+        }
+      }
+      if (pass == 0) {
+        m0 = (n0 > 0) ? a0 / (double)n0 : 0.0;
+        m1 = (n1 > 0) ? a1 / (double)n1 : 0.0;
+      } else {
+        q0 = a0;
+        q1 = a1;
+      }
+    }
+    if (act) {
+      float t = 0.f;
+      if (n0 >= 2 && n1 >= 2) {
+        const double nx = (double)n0, ny = (double)n1;
+        const double sx = sqrt(q0 / (nx - 1.0)), sy = sqrt(q1 / (ny - 1.0));
+        const double d1 = sqrt(((nx - 1.0) * sx * sx + (ny - 1.0) * sy * sy) /
+                               (nx + ny - 2.0));
+        const double d2 = sqrt(1.0 / nx + 1.0 / ny);
+        if (d1 > 0.0) t = (float)fabs((m0 - m1) / d1 / d2);
+      }
+      out[g] = t;
+    }
+  }
 }

@@ -199,15 +199,33 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
     if not ctx.is_primary:
         return result
 
+    # the opt-in device backends of steps 5-6 read W_ih where it already
+    # lives (f32, on the run's device): no host round trip
+    W_dev = None
+    if cfg.kmeans_backend == "hip" or cfg.scoring_backend == "device":
+        W_dev = res.W_ih.float().to(device).contiguous()
+
     log(">>> 5. Find L-groups")
     with timers.phase("lgroups"):
-        lg = find_lgroups(W, freq.cpu().numpy(), cfg.compat_lgroup_bug,
-                          backend=cfg.kmeans_backend, device=device)
+        km_info: Dict = {}
+        lg = find_lgroups(W_dev if cfg.kmeans_backend == "hip" else W,
+                          freq.cpu().numpy(), cfg.compat_lgroup_bug,
+                          backend=cfg.kmeans_backend, device=device,
+                          info=km_info)
+    if km_info:
+        jsonl.emit("kmeans", backend=cfg.kmeans_backend, **km_info)
 
     log(">>> 6. Select biomarkers with gene scores")
     with timers.phase("scoring"):
+        d_all = t_all = None
+        if cfg.scoring_backend == "device":
+            from . import ops
+            d_all = ops.row_norms(W_dev).cpu().numpy()
+            t_all = ops.t_scores(expr_t.float().contiguous(),
+                                 labels_t).cpu().numpy()
         biomarkers = select_biomarkers(W, lg, data["expr"], data["label"],
-                                       data["gene"], cfg.num_biomarker)
+                                       data["gene"], cfg.num_biomarker,
+                                       d_all=d_all, t_all=t_all)
 
     log(">>> 7. Save results")
     with timers.phase("write"):

@@ -1,8 +1,9 @@
-"""Biomarker scoring (reference step 6, G2Vec.py:85-157). Host-side NumPy
-by design (steps 5-6 stay on host — [G]-sized vectors)."""
+"""Biomarker scoring (reference step 6, G2Vec.py:85-157). Host-side NumPy;
+with scoring_backend="device" the two [G] score vectors come from the
+row_norms / t_scores kernels (ops) and only the ranking runs here."""
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -52,9 +53,15 @@ def t_scores(expr: np.ndarray, labels: np.ndarray) -> np.ndarray:
 
 def select_biomarkers(embeddings: np.ndarray, lgroup_idx: np.ndarray,
                       expr: np.ndarray, labels: np.ndarray,
-                      genes: Sequence[str], num_biomarker: int) -> List[str]:
+                      genes: Sequence[str], num_biomarker: int,
+                      d_all: Optional[np.ndarray] = None,
+                      t_all: Optional[np.ndarray] = None) -> List[str]:
     """Top-N per L-group by gene score = 0.5*(minmax d-score + minmax t-score),
-    union sorted (G2Vec.py:85-109)."""
+    union sorted (G2Vec.py:85-109).
+    d_all / t_all: optional precomputed f32 [G] d-scores (embedding row
+    norms) and t-scores over ALL genes; each L-group indexes them in place
+    of computing its own. Both scores are per-gene, so min-max, ranking and
+    top-N are the same arithmetic either way."""
     genes = np.asarray(genes)
     result: List[str] = []
     for grp in (0, 1):      # 0 good, 1 poor
@@ -64,8 +71,10 @@ def select_biomarkers(embeddings: np.ndarray, lgroup_idx: np.ndarray,
         mat = embeddings[sel]
         sub_genes = genes[sel]
         sub_expr = expr[:, sel]
-        d = transform_minmax(np.linalg.norm(mat, axis=1))
-        t = transform_minmax(t_scores(sub_expr, labels))
+        d = transform_minmax(np.linalg.norm(mat, axis=1) if d_all is None
+                             else d_all[sel])
+        t = transform_minmax(t_scores(sub_expr, labels) if t_all is None
+                             else t_all[sel])
         score = 0.5 * (d + t)
         # stable sort desc by score (reference: Python sorted, stable)
         order = np.argsort(-score, kind="stable")[:num_biomarker]

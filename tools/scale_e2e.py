@@ -31,6 +31,10 @@ def main():
     ap.add_argument("--n-modules", type=int, default=64)
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--epochs", type=int, default=30)
+    ap.add_argument("--kmeans", choices=["auto", "sklearn", "torch", "hip"],
+                    default="auto", help="L-group clustering backend")
+    ap.add_argument("--scoring", choices=["host", "device"], default="host",
+                    help="where the d/t-score vectors are computed")
     args = ap.parse_args()
 
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -41,7 +45,8 @@ def main():
     t["synth"] = time.perf_counter() - t0
 
     cfg = G2VecConfig(hidden=args.hidden, epochs=args.epochs, seed=0,
-                      device=str(dev.type))
+                      device=str(dev.type), kmeans_backend=args.kmeans,
+                      scoring_backend=args.scoring)
     expr_t = torch.from_numpy(expr).to(dev)
     labels_t = torch.from_numpy(labels).to(dev)
     edge_t = torch.from_numpy(edge_idx).to(dev)
@@ -60,13 +65,26 @@ def main():
     t["train"] = time.perf_counter() - t0
 
     W = res.W_ih.float().cpu().numpy()
+    W_dev = res.W_ih.float().to(dev).contiguous()
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
     t0 = time.perf_counter()
-    lg = find_lgroups(W, freq.cpu().numpy(), device=dev)
+    km_info = {}
+    lg = find_lgroups(W_dev if cfg.kmeans_backend == "hip" else W,
+                      freq.cpu().numpy(), backend=cfg.kmeans_backend,
+                      device=dev, info=km_info)
     t["lgroups"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
     genes = [f"G{i:07d}" for i in range(n_genes)]
-    bio = select_biomarkers(W, lg, expr, labels, genes, 50)
+    d_all = t_all = None
+    if cfg.scoring_backend == "device":
+        from g2vec_amd import ops
+        d_all = ops.row_norms(W_dev).cpu().numpy()
+        t_all = ops.t_scores(expr_t.float().contiguous(),
+                             labels_t).cpu().numpy()
+    bio = select_biomarkers(W, lg, expr, labels, genes, 50, d_all=d_all,
+                            t_all=t_all)
     t["scoring"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
@@ -77,6 +95,8 @@ def main():
     t["write"] = time.perf_counter() - t0
 
     print({"n_genes": n_genes, "n_paths": ps.n_paths,
+           "kmeans": cfg.kmeans_backend, "scoring": cfg.scoring_backend,
+           **km_info,
            "acc_val": round(res.acc_val, 4), "n_biomarkers": len(bio),
            "lg_counts": np.bincount(lg, minlength=3).tolist(),
            "timers_s": {k: round(v, 2) for k, v in t.items()}})
