@@ -79,6 +79,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "(auto = on at >= 100k genes; pure layout change)")
     p.add_argument("--no-hipgraph", action="store_true",
                    help="disable hipGraph capture of the training epoch")
+    p.add_argument("--write-scores", action="store_true",
+                   help="also write RESULT_NAME_scores.txt: per-gene d-score, "
+                        "t-score, gene score and biomarker flag")
+    p.add_argument("--permutations", type=int, default=0, metavar="B",
+                   help="label-permutation p-values of the t-scores over B "
+                        "relabellings (p_perm, q_bh, p_maxT columns of the "
+                        "scores table; implies --write-scores; 0 = off)")
+    p.add_argument("--perm-seed", type=int, default=None,
+                   help="seed of the relabellings (default: --seed)")
     p.add_argument("--save-paths", type=str, default="")
     p.add_argument("--load-model", type=str, default="",
                    help="skip training: load W_ih from a --save-model .pt "
@@ -110,7 +119,9 @@ def args_to_config(a: argparse.Namespace) -> G2VecConfig:
         load_paths=a.load_paths, save_model=a.save_model,
         load_model=a.load_model,
         log_jsonl=a.log_jsonl,
-        use_hipgraph=not a.no_hipgraph)
+        use_hipgraph=not a.no_hipgraph,
+        write_scores=a.write_scores or a.permutations > 0,
+        permutations=a.permutations, perm_seed=a.perm_seed)
 
 
 def main(argv=None) -> int:

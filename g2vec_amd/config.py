@@ -90,6 +90,12 @@ class G2VecConfig:
                                     # trainer; outputs are unchanged up to
                                     # fp32 reduction order.
     use_hipgraph: bool = True       # record the full-batch epoch into a hipGraph
+    write_scores: bool = False      # also write <name>_scores.txt: per-gene
+                                    # d/t/gene scores behind the selection
+    permutations: int = 0           # B > 0: label-permutation p-values of the
+                                    # t-scores over B relabellings, added to
+                                    # the scores table (implies write_scores)
+    perm_seed: Optional[int] = None  # seed of the relabellings; None = seed
 
     def validate(self) -> None:
         if self.hidden not in (64, 128, 256, 512, 1024):
@@ -133,6 +139,12 @@ class G2VecConfig:
             raise ValueError(f"bad scoring_backend {self.scoring_backend}")
         if self.gene_relabel not in ("auto", "on", "off"):
             raise ValueError(f"bad gene_relabel {self.gene_relabel}")
+        if self.permutations < 0:
+            raise ValueError("permutations must be >= 0 (0 = off)")
+        if self.perm_seed is not None and self.perm_seed < 0:
+            raise ValueError("perm_seed must be >= 0")
+        if self.permutations > 0:
+            self.write_scores = True
 
 
 def resolve_device(device: str) -> str:

@@ -3,10 +3,11 @@
   *_biomarkers.txt  G2Vec.py:127-131
   *_lgroups.txt     G2Vec.py:159-165
   *_vectors.txt     G2Vec.py:203-215 (values printed \t%.6f)
+  *_scores.txt      opt-in per-gene scores table (not in the reference)
 """
 from __future__ import annotations
 
-from typing import Iterable, Sequence
+from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
@@ -54,4 +55,34 @@ def write_vectors(result_name: str, mat: np.ndarray, genes: Sequence[str],
         f.write(header)
         f.write("\n".join(rows))
         f.write("\n")
+    return out
+
+
+def write_scores(result_name: str, genes: Sequence[str],
+                 lgroup_idx: Sequence[int], scores: dict,
+                 perm: Optional[dict] = None) -> str:
+    """<name>_scores.txt: one tab-separated row per gene, in gene order.
+    Columns GeneSymbol, Lgroup, d_score, t_score (raw values), gene_score
+    (the within-L-group 0.5*(minmax d + minmax t) the selection ranks by; NA
+    outside L-groups 0 and 1), biomarker (0/1) and, with perm (the dict of
+    scoring.permutation_pvalues), p_perm, q_bh, p_maxT. Scores are printed
+    %.6f, p-values %.6g."""
+    out = result_name + "_scores.txt"
+    cols = ["GeneSymbol", "Lgroup", "d_score", "t_score", "gene_score",
+            "biomarker"]
+    if perm is not None:
+        cols += ["p_perm", "q_bh", "p_maxT"]
+    gs = np.asarray(scores["gene_score"], dtype=np.float64)
+    with open(out, "w") as f:
+        f.write("\t".join(cols) + "\n")
+        for i, gene in enumerate(genes):
+            row = [str(gene), "%d" % int(lgroup_idx[i]),
+                   "%.6f" % float(scores["d_score"][i]),
+                   "%.6f" % float(scores["t_score"][i]),
+                   "NA" if np.isnan(gs[i]) else "%.6f" % gs[i],
+                   "%d" % int(scores["is_biomarker"][i])]
+            if perm is not None:
+                row += ["%.6g" % float(perm[k][i])
+                        for k in ("p", "q_bh", "p_maxT")]
+            f.write("\t".join(row) + "\n")
     return out

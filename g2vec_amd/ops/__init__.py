@@ -339,3 +339,88 @@ def t_scores(expr, labels) -> torch.Tensor:
         native().t_scores_(expr, labels, out)
         return out
     return cpu_ref.t_scores(expr, labels)
+
+
+# ------------------------------------------------------------------ step 6: permutation null of t
+def _perm_check(expr, masks) -> int:
+    """The guards both perm_t entry points share, before any launch; returns
+    n1, the number of poor-group samples every mask row carries."""
+    if expr.dtype != torch.float32 or expr.dim() != 2:
+        raise ValueError("expr must be a float32 [S, G] tensor")
+    if masks.dtype != torch.uint8 or masks.dim() != 2:
+        raise ValueError("masks must be a uint8 [B, S] tensor")
+    if not expr.is_contiguous() or not masks.is_contiguous():
+        raise ValueError("expr and masks must be contiguous")
+    if masks.device != expr.device:
+        raise ValueError("expr and masks must be on the same device")
+    S = expr.shape[0]
+    if masks.shape[1] != S:
+        raise ValueError(f"masks has {masks.shape[1]} columns, expr has "
+                         f"{S} samples")
+    if S < 4:
+        raise ValueError("the pooled t needs S >= 4 samples")
+    if masks.shape[0] == 0:
+        raise ValueError("masks has no rows")
+    if int(masks.max()) > 1:
+        raise ValueError("masks must hold only 0 and 1")
+    rows = masks.sum(dim=1, dtype=torch.int64)
+    n1, n1_hi = int(rows.min()), int(rows.max())
+    if n1 != n1_hi:
+        raise ValueError(f"every mask row must mark the same number of "
+                         f"samples, got {n1} to {n1_hi}")
+    if n1 < 2 or S - n1 < 2:
+        raise ValueError(f"each group needs >= 2 samples, masks give "
+                         f"{S - n1} / {n1}")
+    return n1
+
+
+def col_moments(expr):
+    """(T, Q) f64 [G]: f64-accumulated column sums of x and of the f32
+    product x*x of expr f32 [S, G]."""
+    if expr.is_cuda:
+        G = expr.shape[1]
+        T = torch.empty(G, dtype=torch.float64, device=expr.device)
+        Q = torch.empty(G, dtype=torch.float64, device=expr.device)
+        native().col_moments_(expr, T, Q)
+        return T, Q
+    return cpu_ref.col_moments(expr)
+
+
+def perm_t_stats(expr, masks) -> torch.Tensor:
+    """stat f64 [B, G] = t^2 of the pooled two-sample t of every gene column
+    of expr f32 [S, G] (centred per gene by the caller) under every 0/1 row
+    of masks u8 [B, S] (1 = poor group). 0 where the pooled variance is
+    <= 0. All rows must mark the same n1 >= 2 samples and leave >= 2. Meant
+    for small B: the observed labelling and tests."""
+    n1 = _perm_check(expr, masks)
+    if expr.is_cuda:
+        T, Q = col_moments(expr)
+        out = torch.empty(masks.shape[0], expr.shape[1], dtype=torch.float64,
+                          device=expr.device)
+        native().perm_t_stats_(expr, masks, T, Q, n1, out)
+        return out
+    return cpu_ref.perm_t_stats(expr, masks, n1)
+
+
+def perm_t_counts(expr, masks, stat_obs, moments=None):
+    """(counts i32 [G], maxstat f64 [B]): counts[g] = number of mask rows
+    whose stat[b, g] >= stat_obs[g] * (1 - 2^-30), maxstat[b] = max_g
+    stat[b, g]; the same arithmetic as perm_t_stats, nothing of size G x B
+    written. moments: optional (T, Q) from col_moments(expr), to share them
+    between calls over mask chunks (GPU)."""
+    n1 = _perm_check(expr, masks)
+    G = expr.shape[1]
+    if (stat_obs.dtype != torch.float64 or stat_obs.shape != (G,)
+            or not stat_obs.is_contiguous()
+            or stat_obs.device != expr.device):
+        raise ValueError("stat_obs must be a contiguous float64 [G] tensor "
+                         "on expr's device")
+    if expr.is_cuda:
+        T, Q = moments if moments is not None else col_moments(expr)
+        counts = torch.empty(G, dtype=torch.int32, device=expr.device)
+        maxstat = torch.empty(masks.shape[0], dtype=torch.float64,
+                              device=expr.device)
+        native().perm_t_counts_(expr, masks, T, Q, n1, stat_obs, counts,
+                                maxstat)
+        return counts, maxstat
+    return cpu_ref.perm_t_counts(expr, masks, n1, stat_obs)

@@ -320,3 +320,67 @@ def t_scores(expr: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     pos = d1 > 0.0
     t = torch.where(pos, (mx - my) / torch.where(pos, d1, 1.0) / d2, 0.0)
     return t.abs().float()
+
+
+# ------------------------------------------------------------------ step 6: permutation null of t
+def splitmix64_vec(state: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """splitmix64 over a uint64 array: (new_state, random_u64), element by
+    element the same bits as the scalar `splitmix64`."""
+    state = np.asarray(state, dtype=np.uint64) + _SM64_GAMMA   # wraps mod 2^64
+    z = state.copy()
+    z = (z ^ (z >> np.uint64(30))) * _SM64_M1
+    z = (z ^ (z >> np.uint64(27))) * _SM64_M2
+    z = z ^ (z >> np.uint64(31))
+    return state, z
+
+
+PERM_TIE = 1.0 - 2.0 ** -30     # exceed: stat_perm >= stat_obs * PERM_TIE
+
+
+def col_moments(expr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(T, Q) f64 [G]: column sums of x and of the f32 product x*x of
+    expr f32 [S, G], accumulated in f64 (col_moments_kernel)."""
+    return expr.double().sum(dim=0), (expr * expr).double().sum(dim=0)
+
+
+def _perm_t_block(expr, x2, masks, T, Q, n1: int) -> torch.Tensor:
+    """stat f64 [B, G] of perm_t_body: f32 matmuls for s1 and q1, then the
+    f64 formula (0 when pooled <= 0)."""
+    S = expr.shape[0]
+    mf = masks.float()
+    s1 = (mf @ expr).double()
+    q1 = (mf @ x2).double()
+    n1f, n0f = float(n1), float(S - n1)
+    s0, q0 = T - s1, Q - q1
+    ss = (q1 - s1 * s1 / n1f) + (q0 - s0 * s0 / n0f)
+    pooled = ss / float(S - 2)
+    d = s0 / n0f - s1 / n1f
+    pos = pooled > 0.0
+    return torch.where(
+        pos, d * d / torch.where(pos, pooled, 1.0) / (1.0 / n1f + 1.0 / n0f),
+        0.0)
+
+
+def perm_t_stats(expr: torch.Tensor, masks: torch.Tensor,
+                 n1: int) -> torch.Tensor:
+    T, Q = col_moments(expr)
+    return _perm_t_block(expr, expr * expr, masks, T, Q, n1)
+
+
+def perm_t_counts(expr: torch.Tensor, masks: torch.Tensor, n1: int,
+                  stat_obs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(counts i32 [G], maxstat f64 [B]); walks the masks in row blocks so
+    nothing of size G x B is held."""
+    T, Q = col_moments(expr)
+    x2 = expr * expr
+    thr = stat_obs * PERM_TIE
+    B, G = masks.shape[0], expr.shape[1]
+    counts = torch.zeros(G, dtype=torch.int64)
+    maxstat = torch.zeros(B, dtype=torch.float64)
+    blk = max(1, min(B, (1 << 22) // max(G, 1)))
+    for lo in range(0, B, blk):
+        st = _perm_t_block(expr, x2, masks[lo:lo + blk], T, Q, n1)
+        counts += (st >= thr).sum(dim=0)
+        if G > 0:
+            maxstat[lo:lo + blk] = st.max(dim=1).values
+    return counts.int(), maxstat

@@ -678,6 +678,110 @@ void t_scores_(torch::Tensor expr, torch::Tensor labels, torch::Tensor out) {
   LAUNCH_CHECK();
 }
 
+// ------------------------------------------- step 6: permutation null of t
+inline void check_gfx950(const char* op) {
+  // the MFMA body is compiled only for gfx950: elsewhere the launch would be
+  // a no-op leaving the outputs unwritten
+  hipDeviceProp_t prop;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipGetDeviceProperties(&prop, dev);
+  TORCH_CHECK(std::string(prop.gcnArchName).rfind("gfx950", 0) == 0, op,
+              ": MFMA kernel is gfx950-only, device reports ",
+              prop.gcnArchName);
+}
+
+void col_moments_(torch::Tensor expr, torch::Tensor T, torch::Tensor Q) {
+  CHECK_F32(expr); CHECK_F64(T); CHECK_F64(Q);
+  TORCH_CHECK(expr.dim() == 2, "expr must be [S, G]");
+  const long long S = expr.size(0);
+  const long long G = expr.size(1);
+  TORCH_CHECK(S >= 1 && S < (1LL << 31), "expr needs 1 <= S < 2^31 rows");
+  TORCH_CHECK(T.dim() == 1 && T.numel() == G && Q.dim() == 1 &&
+                  Q.numel() == G,
+              "T and Q must be [G]");
+  if (G == 0) return;
+  hipLaunchKernelGGL(col_moments_kernel, dim3(grid_for(G, 256)), dim3(256), 0,
+                     cur_stream(), expr.data_ptr<float>(), (int)S, G,
+                     T.data_ptr<double>(), Q.data_ptr<double>());
+  LAUNCH_CHECK();
+}
+
+// shared guards of the two perm_t entry points; returns the launch grid
+inline dim3 perm_t_check(const char* op, const torch::Tensor& expr,
+                         const torch::Tensor& masks, const torch::Tensor& T,
+                         const torch::Tensor& Q, int64_t n1) {
+  CHECK_F32(expr); CHECK_GPU_CONT(masks); CHECK_F64(T); CHECK_F64(Q);
+  TORCH_CHECK(masks.scalar_type() == at::kByte, "masks must be uint8");
+  TORCH_CHECK(expr.dim() == 2, "expr must be [S, G]");
+  TORCH_CHECK(masks.dim() == 2, "masks must be [B, S]");
+  const long long S = expr.size(0);
+  const long long G = expr.size(1);
+  const long long B = masks.size(0);
+  TORCH_CHECK(masks.size(1) == S, op, ": masks has ", masks.size(1),
+              " columns, expr has ", S, " samples");
+  TORCH_CHECK(S >= 4 && S < (1LL << 31), op, " needs 4 <= S < 2^31 samples");
+  TORCH_CHECK(n1 >= 2 && S - n1 >= 2, op,
+              " needs at least 2 samples in each group");
+  TORCH_CHECK(T.dim() == 1 && T.numel() == G && Q.dim() == 1 &&
+                  Q.numel() == G,
+              "T and Q must be [G]");
+  check_gfx950(op);
+  const long long ngt = (G + 63) / 64;
+  const long long nbt = (B + 63) / 64;
+  TORCH_CHECK(ngt < (1LL << 31), op, ": too many genes");
+  // enough blocks to fill the device; each walks its share of the
+  // relabelling tiles against one gene tile
+  long long gy = ngt > 0 ? (2048 + ngt - 1) / ngt : 1;
+  if (gy > nbt) gy = nbt;
+  if (gy > 65535) gy = 65535;
+  if (gy < 1) gy = 1;
+  return dim3((unsigned)ngt, (unsigned)gy);
+}
+
+void perm_t_stats_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
+                   torch::Tensor Q, int64_t n1, torch::Tensor out) {
+  const dim3 grid = perm_t_check("perm_t_stats", expr, masks, T, Q, n1);
+  CHECK_F64(out);
+  const long long S = expr.size(0), G = expr.size(1), B = masks.size(0);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) == G,
+              "out must be [B, G]");
+  if (G == 0 || B == 0) return;
+  hipLaunchKernelGGL(perm_t_stats_kernel, grid, dim3(256), 0, cur_stream(),
+                     expr.data_ptr<float>(), masks.data_ptr<uint8_t>(),
+                     T.data_ptr<double>(), Q.data_ptr<double>(), (int)S, G, B,
+                     (int)n1, out.data_ptr<double>());
+  LAUNCH_CHECK();
+}
+
+void perm_t_counts_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
+                    torch::Tensor Q, int64_t n1, torch::Tensor stat_obs,
+                    torch::Tensor counts, torch::Tensor maxstat) {
+  const dim3 grid = perm_t_check("perm_t_counts", expr, masks, T, Q, n1);
+  CHECK_F64(stat_obs); CHECK_I32(counts); CHECK_F64(maxstat);
+  const long long S = expr.size(0), G = expr.size(1), B = masks.size(0);
+  TORCH_CHECK(stat_obs.dim() == 1 && stat_obs.numel() == G,
+              "stat_obs must be [G]");
+  TORCH_CHECK(counts.dim() == 1 && counts.numel() == G, "counts must be [G]");
+  TORCH_CHECK(maxstat.dim() == 1 && maxstat.numel() == B,
+              "maxstat must be [B]");
+  // the kernel folds into both through integer atomics
+  if (G > 0)
+    C10_HIP_CHECK(hipMemsetAsync(counts.data_ptr<int>(), 0, G * sizeof(int),
+                                 cur_stream()));
+  if (B > 0)
+    C10_HIP_CHECK(hipMemsetAsync(maxstat.data_ptr<double>(), 0,
+                                 B * sizeof(double), cur_stream()));
+  if (G == 0 || B == 0) return;
+  hipLaunchKernelGGL(
+      perm_t_counts_kernel, grid, dim3(256), 0, cur_stream(),
+      expr.data_ptr<float>(), masks.data_ptr<uint8_t>(), T.data_ptr<double>(),
+      Q.data_ptr<double>(), stat_obs.data_ptr<double>(), (int)S, G, B, (int)n1,
+      counts.data_ptr<int>(),
+      reinterpret_cast<unsigned long long*>(maxstat.data_ptr<double>()));
+  LAUNCH_CHECK();
+}
+
 // ------------------------------------------------- native host TSV parser
 std::tuple<std::vector<std::string>, std::vector<std::string>, torch::Tensor>
 parse_expression_tsv(const std::string& path) {
@@ -800,6 +904,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "d2 = min(d2, |x - c|^2) for one new centre (k-means++)");
   m.def("row_norms_", &row_norms_, "row L2 norms, f64-accumulated (out-arg)");
   m.def("t_scores_", &t_scores_, "|pooled t| per gene column (out-arg)");
+  m.def("col_moments_", &col_moments_,
+        "f64 column sums of x and x*x (out-args)");
+  m.def("perm_t_stats_", &perm_t_stats_,
+        "t^2 per (relabelling, gene), MFMA f32 (out-arg)");
+  m.def("perm_t_counts_", &perm_t_counts_,
+        "per-gene exceed counts + per-relabelling max t^2 (out-args)");
   m.def("parse_expression_tsv", &parse_expression_tsv,
         "native expression TSV parser");
 }

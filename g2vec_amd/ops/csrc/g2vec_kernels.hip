@@ -28,6 +28,9 @@
 //   kmeans_mind2_kernel<HPL>    (step 5) k-means++ support: d2 = min(d2, |x - c|^2)
 //   row_norms_kernel<HPL>       (step 6) d-score: f64-accumulated row L2 norms
 //   t_scores_kernel             (step 6) |pooled t| per gene column, f64 two-pass
+//   col_moments_kernel          (step 6) f64 column sums of x and x*x for the permutation null
+//   perm_t_stats_kernel         (step 6) t^2 per (relabelling, gene) on v_mfma_f32_16x16x4_f32
+//   perm_t_counts_kernel        same body: per-gene exceed counts + per-relabelling max, no G x B output
 //
 // The templates are instantiated by their launch sites in bindings.hip, the
 // one translation unit that includes this file.
@@ -1359,4 +1362,246 @@ t_scores_kernel(const float* __restrict__ expr, const int* __restrict__ labels,
       out[g] = t;
     }
   }
+}
+
+// ============================== step 6: label-permutation null of the pooled t
+// For a 0/1 mask m over the S samples (poor group m == 1, n1 = sum m,
+// n0 = S - n1) and gene g of expr[S, G]:
+//   s1 = sum_s x m      q1 = sum_s (x x) m     f32 accumulate (MFMA)
+//   T  = sum_s x        Q  = sum_s (x x)       f64 accumulate of the f32 values
+//   s0 = T - s1, q0 = Q - q1                   f64 from here on
+//   ss = (q1 - s1 s1 / n1) + (q0 - s0 s0 / n0),  pooled = ss / (S - 2)
+//   d  = s0 / n0 - s1 / n1
+//   stat = pooled > 0 ? d d / pooled / (1/n1 + 1/n0) : 0          ( = t^2 )
+// A relabelling EXCEEDS when stat >= stat_obs * (1 - 2^-30): the factor only
+// merges values equal in exact arithmetic but ulps apart in evaluation.
+
+// T and Q per gene column. One THREAD per gene (each sample row a coalesced
+// read, as in t_scores_kernel); x*x is one f32 multiply, like the q1 operand.
+extern "C" __global__ void __launch_bounds__(256)
+col_moments_kernel(const float* __restrict__ expr, int S, long long G,
+                   double* __restrict__ T, double* __restrict__ Q) {
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += (long long)gridDim.x * blockDim.x) {
+    double t = 0.0, q = 0.0;
+    const float* col = expr + g;
+#pragma unroll 4
+    for (int s = 0; s < S; ++s) {
+      const float v = col[(long long)s * G];
+      const float v2 = v * v;
+      t += (double)v;
+      q += (double)v2;
+    }
+    T[g] = t;
+    Q[g] = q;
+  }
+}
+
+#define PT_TILE 64                 // genes x relabellings per block
+#define PT_KC 64                   // samples per LDS-staged K chunk
+#define PT_NLD (PT_TILE * PT_KC / 256)   // staged elements per thread and tile
+#define PT_LDX (PT_TILE + 16)      // x tile [k][gene]: stride = 16 mod 32 banks
+#define PT_LDM (PT_KC + 2)         // mask tile [relabelling][k]: stride = 2 mod 32
+
+__device__ __forceinline__ double perm_t_stat(double s1, double q1, double T,
+                                              double Q, double n1, double n0,
+                                              double dof, double inv_n) {
+  const double s0 = T - s1, q0 = Q - q1;
+  const double ss = (q1 - s1 * s1 / n1) + (q0 - s0 * s0 / n0);
+  const double pooled = ss / dof;
+  const double d = s0 / n0 - s1 / n1;
+  return pooled > 0.0 ? d * d / pooled / inv_n : 0.0;
+}
+
+// One body for the two entry points below, so the stat of a (gene, mask)
+// pair is the same code and the same bits in both modes.
+// 64 genes x 64 relabellings per 256-thread block; wave w owns the 32x32
+// sub-tile (w>>1, w&1) as 2x2 fragments of v_mfma_f32_16x16x4_f32, each with
+// an s1 and a q1 accumulator (8 independent MFMA chains per wave). The q1
+// A-operand is av*av formed in-register: no x^2 tile anywhere. K runs over S
+// in PT_KC-sample chunks staged in LDS (x tile k-major, as expr rows are
+// gene-contiguous; u8 masks widened to f32 once, at the stage), zero-padded
+// to a multiple of 4. The global loads of the NEXT chunk (or of the next
+// relabelling tile's first chunk) are issued into registers before the MFMA
+// loop of the current one and land in LDS after it, so their latency hides
+// behind the matrix work. blockIdx.x is the gene tile; the block walks the
+// relabelling tiles blockIdx.y, +gridDim.y, ...
+// stat_out != null: stats mode, stat_out[b, g] = stat.
+// else counts mode: counts[g] += #{b : stat >= thr_g}, maxstat[b] =
+// max(maxstat[b], max_g stat) through integer atomics (order-independent;
+// non-negative doubles order like their u64 bit patterns), both zeroed by
+// the host first.
+__device__ __forceinline__ void
+perm_t_body(const float* __restrict__ expr, const uint8_t* __restrict__ masks,
+            const double* __restrict__ T, const double* __restrict__ Q,
+            const double* __restrict__ stat_obs, int S, long long G,
+            long long B, int n1i, double* __restrict__ stat_out,
+            int* __restrict__ counts,
+            unsigned long long* __restrict__ maxstat) {
+#if defined(__gfx950__)
+  __shared__ float Xs[PT_KC * PT_LDX];
+  __shared__ float Ms[PT_TILE * PT_LDM];
+  __shared__ double Tq[3][PT_TILE];            // T, Q, exceed threshold
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1;
+  const int fr = lane & 15, kk = lane >> 4;
+  const long long g0 = (long long)blockIdx.x * PT_TILE;
+  const double n1 = (double)n1i, n0 = (double)(S - n1i);
+  const double dof = (double)(S - 2), inv_n = 1.0 / n1 + 1.0 / n0;
+
+  if (threadIdx.x < PT_TILE) {
+    const long long g = g0 + threadIdx.x;
+    const bool in = g < G;
+    Tq[0][threadIdx.x] = in ? T[g] : 0.0;
+    Tq[1][threadIdx.x] = in ? Q[g] : 0.0;
+    Tq[2][threadIdx.x] =
+        (in && stat_obs) ? stat_obs[g] * (1.0 - 0x1p-30) : 0.0;
+  }
+
+  int cnt[2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cnt[a][r] = 0;
+
+  // staging registers: element (hi, lo) = (4 * i + wid, lane) of the 64 x 64
+  // chunk; hi is the sample of the x tile and the relabelling of the mask
+  // tile, lo the gene resp. the sample. Out-of-range elements load as zero.
+  float xr[PT_NLD];
+  uint8_t mr[PT_NLD];
+  auto prefetch = [&](long long pb0, int ps0) {
+#pragma unroll
+    for (int i = 0; i < PT_NLD; ++i) {
+      const int hi = 4 * i + wid;
+      xr[i] = (ps0 + hi < S && g0 + lane < G)
+          ? expr[(long long)(ps0 + hi) * G + g0 + lane] : 0.f;
+      mr[i] = (pb0 + hi < B && ps0 + lane < S)
+          ? masks[(pb0 + hi) * S + ps0 + lane] : (uint8_t)0;
+    }
+  };
+
+  const long long nbt = (B + PT_TILE - 1) / PT_TILE;
+  if ((long long)blockIdx.y < nbt) prefetch((long long)blockIdx.y * PT_TILE, 0);
+  for (long long bt = blockIdx.y; bt < nbt; bt += gridDim.y) {
+    const long long b0 = bt * PT_TILE;
+    f32x4 acs[2][2], acq[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        acs[a][b] = (f32x4)(0.f);
+        acq[a][b] = (f32x4)(0.f);
+      }
+
+    for (int s0 = 0; s0 < S; s0 += PT_KC) {
+      const int kc = (S - s0 < PT_KC) ? S - s0 : PT_KC;
+      const int kc4 = (kc + 3) & ~3;
+      __syncthreads();                   // readers of the last chunk done
+#pragma unroll
+      for (int i = 0; i < PT_NLD; ++i) {
+        const int hi = 4 * i + wid;
+        Xs[hi * PT_LDX + lane] = xr[i];
+        Ms[hi * PT_LDM + lane] = (float)mr[i];
+      }
+      __syncthreads();
+      if (s0 + PT_KC < S)
+        prefetch(b0, s0 + PT_KC);
+      else if (bt + gridDim.y < nbt)
+        prefetch((bt + gridDim.y) * PT_TILE, 0);
+      for (int k0 = 0; k0 < kc4; k0 += 4) {
+        float av[2], aq[2], bv[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          av[a] = Xs[(k0 + kk) * PT_LDX + wr * 32 + a * 16 + fr];
+          aq[a] = av[a] * av[a];
+        }
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+          bv[b] = Ms[(wc * 32 + b * 16 + fr) * PT_LDM + k0 + kk];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            acs[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                av[a], bv[b], acs[a][b], 0, 0, 0);
+            acq[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                aq[a], bv[b], acq[a][b], 0, 0, 0);
+          }
+      }
+    }
+
+    // C/D map (16x16): col = lane&15 (relabelling), row = (lane>>4)*4 + reg
+    // (gene). Padded genes and relabellings are computed and dropped here.
+    double cmax[2] = {0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int gl = wr * 32 + a * 16 + kk * 4 + reg;
+        const bool g_in = g0 + gl < G;
+        const double Tg = Tq[0][gl], Qg = Tq[1][gl], thr = Tq[2][gl];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const long long bb = b0 + wc * 32 + b * 16 + fr;
+          const double st = perm_t_stat((double)acs[a][b][reg],
+                                        (double)acq[a][b][reg], Tg, Qg, n1,
+                                        n0, dof, inv_n);
+          const bool live = g_in && bb < B;
+          if (stat_out) {
+            if (live) stat_out[bb * G + g0 + gl] = st;
+          } else {
+            cnt[a][reg] += (live && st >= thr) ? 1 : 0;
+            cmax[b] = (live && st > cmax[b]) ? st : cmax[b];
+          }
+        }
+      }
+    if (!stat_out) {
+      // column max: over the 4 lane groups that hold one relabelling
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        double m = cmax[b];
+        m = fmax(m, __shfl_xor(m, 16));
+        m = fmax(m, __shfl_xor(m, 32));
+        const long long bb = b0 + wc * 32 + b * 16 + fr;
+        if (kk == 0 && bb < B && m > 0.0)
+          atomicMax(&maxstat[bb], (unsigned long long)__double_as_longlong(m));
+      }
+    }
+  }
+  if (!stat_out) {
+    // exceed counts: over the 16 lanes that share a gene row
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        int c = cnt[a][reg];
+        for (int o = 1; o < 16; o <<= 1) c += __shfl_xor(c, o);
+        const long long g = g0 + wr * 32 + a * 16 + kk * 4 + reg;
+        if (fr == 0 && g < G && c) atomicAdd(&counts[g], c);
+      }
+  }
+#endif
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+perm_t_stats_kernel(const float* __restrict__ expr,
+                    const uint8_t* __restrict__ masks,
+                    const double* __restrict__ T, const double* __restrict__ Q,
+                    int S, long long G, long long B, int n1,
+                    double* __restrict__ stat_out) {
+  perm_t_body(expr, masks, T, Q, nullptr, S, G, B, n1, stat_out, nullptr,
+              nullptr);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+perm_t_counts_kernel(const float* __restrict__ expr,
+                     const uint8_t* __restrict__ masks,
+                     const double* __restrict__ T, const double* __restrict__ Q,
+                     const double* __restrict__ stat_obs, int S, long long G,
+                     long long B, int n1, int* __restrict__ counts,
+                     unsigned long long* __restrict__ maxstat) {
+  perm_t_body(expr, masks, T, Q, stat_obs, S, G, B, n1, nullptr, counts,
+              maxstat);
 }

@@ -20,7 +20,7 @@ from .graph import build_group_graph
 from .models.cbow import CbowTrainer
 from .parallel.dist import DistContext, single
 from .paths import PathSet, integrate_pathsets
-from .scoring import select_biomarkers
+from .scoring import permutation_pvalues, score_genes, select_biomarkers
 from .utils.obs import JsonlLogger, PhaseTimers
 from .walks import WalkSet, generate_walks
 
@@ -223,9 +223,28 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
             d_all = ops.row_norms(W_dev).cpu().numpy()
             t_all = ops.t_scores(expr_t.float().contiguous(),
                                  labels_t).cpu().numpy()
-        biomarkers = select_biomarkers(W, lg, data["expr"], data["label"],
-                                       data["gene"], cfg.num_biomarker,
-                                       d_all=d_all, t_all=t_all)
+        scores = perm = None
+        if cfg.write_scores:
+            scores = score_genes(W, lg, data["expr"], data["label"],
+                                 data["gene"], cfg.num_biomarker,
+                                 d_all=d_all, t_all=t_all)
+            biomarkers = scores["biomarkers"]
+        else:
+            biomarkers = select_biomarkers(W, lg, data["expr"], data["label"],
+                                           data["gene"], cfg.num_biomarker,
+                                           d_all=d_all, t_all=t_all)
+    if cfg.permutations > 0:
+        perm_seed = cfg.perm_seed if cfg.perm_seed is not None else (
+            cfg.seed if cfg.seed is not None
+            else int(time.time_ns() & 0x7FFFFFFF))
+        t0 = time.perf_counter()
+        with timers.phase("permutations"):
+            perm = permutation_pvalues(data["expr"], np.asarray(data["label"]),
+                                       cfg.permutations, perm_seed,
+                                       device=device)
+        jsonl.emit("perm", B=cfg.permutations, seed=perm_seed,
+                   seconds=time.perf_counter() - t0,
+                   n_q05=int(np.sum(perm["q_bh"] <= 0.05)))
 
     log(">>> 7. Save results")
     with timers.phase("write"):
@@ -235,6 +254,10 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
         log("    %s" % f2)
         f3 = gio.write_vectors(cfg.result_name, W, data["gene"])
         log("    %s" % f3)
+        if scores is not None:
+            f4 = gio.write_scores(cfg.result_name, data["gene"], lg, scores,
+                                  perm)
+            log("    %s" % f4)
 
     result.update({"lgroups": lg, "biomarkers": biomarkers,
                    "timers": timers.summary()})
