@@ -88,6 +88,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "scores table; implies --write-scores; 0 = off)")
     p.add_argument("--perm-seed", type=int, default=None,
                    help="seed of the relabellings (default: --seed)")
+    p.add_argument("--neighbors", type=int, default=0, metavar="K",
+                   help="also write RESULT_NAME_neighbors.txt: the K nearest "
+                        "genes (cosine over the embedding) of every query "
+                        "gene (1..64; 0 = off)")
+    p.add_argument("--neighbors-of", choices=["biomarkers", "all"],
+                   default="biomarkers",
+                   help="query genes of --neighbors: the selected biomarkers "
+                        "or every gene")
     p.add_argument("--save-paths", type=str, default="")
     p.add_argument("--load-model", type=str, default="",
                    help="skip training: load W_ih from a --save-model .pt "
@@ -121,7 +129,8 @@ def args_to_config(a: argparse.Namespace) -> G2VecConfig:
         log_jsonl=a.log_jsonl,
         use_hipgraph=not a.no_hipgraph,
         write_scores=a.write_scores or a.permutations > 0,
-        permutations=a.permutations, perm_seed=a.perm_seed)
+        permutations=a.permutations, perm_seed=a.perm_seed,
+        neighbors=a.neighbors, neighbors_of=a.neighbors_of)
 
 
 def main(argv=None) -> int:

@@ -96,6 +96,11 @@ class G2VecConfig:
                                     # t-scores over B relabellings, added to
                                     # the scores table (implies write_scores)
     perm_seed: Optional[int] = None  # seed of the relabellings; None = seed
+    neighbors: int = 0              # K > 0: also write <name>_neighbors.txt,
+                                    # the K nearest genes (cosine over W_ih)
+                                    # of every query gene (neighbors.py)
+    neighbors_of: str = "biomarkers"  # query set: "biomarkers" (file order)
+                                    # | "all" (every gene, gene order)
 
     def validate(self) -> None:
         if self.hidden not in (64, 128, 256, 512, 1024):
@@ -145,6 +150,10 @@ class G2VecConfig:
             raise ValueError("perm_seed must be >= 0")
         if self.permutations > 0:
             self.write_scores = True
+        if not 0 <= self.neighbors <= 64:
+            raise ValueError("neighbors must be in [0, 64] (0 = off)")
+        if self.neighbors_of not in ("biomarkers", "all"):
+            raise ValueError(f"bad neighbors_of {self.neighbors_of}")
 
 
 def resolve_device(device: str) -> str:

@@ -4,6 +4,7 @@
   *_lgroups.txt     G2Vec.py:159-165
   *_vectors.txt     G2Vec.py:203-215 (values printed \t%.6f)
   *_scores.txt      opt-in per-gene scores table (not in the reference)
+  *_neighbors.txt   opt-in nearest-gene table (not in the reference)
 """
 from __future__ import annotations
 
@@ -85,4 +86,29 @@ def write_scores(result_name: str, genes: Sequence[str],
                 row += ["%.6g" % float(perm[k][i])
                         for k in ("p", "q_bh", "p_maxT")]
             f.write("\t".join(row) + "\n")
+    return out
+
+
+def write_neighbors(result_name: str, genes: Sequence[str],
+                    queries: Sequence[int], idx: np.ndarray, sim: np.ndarray,
+                    lgroup_idx: Sequence[int],
+                    biomarkers: Iterable[str]) -> str:
+    """<name>_neighbors.txt: for every query gene (row index into genes, in
+    the given order) its nearest genes from neighbors.nearest_genes (idx,
+    sim [Q, K]), best first. Columns GeneSymbol, Rank (1..K), Neighbor,
+    Cosine (%.6f), NeighborLgroup, NeighborBiomarker (0/1). Missing
+    neighbours (idx == -1) are omitted."""
+    out = result_name + "_neighbors.txt"
+    bio = set(biomarkers)
+    with open(out, "w") as f:
+        f.write("GeneSymbol\tRank\tNeighbor\tCosine\tNeighborLgroup\t"
+                "NeighborBiomarker\n")
+        for q, row_i, row_s in zip(queries, idx, sim):
+            for rank, (g, s) in enumerate(zip(row_i, row_s), start=1):
+                if g < 0:
+                    continue
+                name = str(genes[int(g)])
+                f.write("%s\t%d\t%s\t%.6f\t%d\t%d\n"
+                        % (genes[int(q)], rank, name, float(s),
+                           int(lgroup_idx[int(g)]), int(name in bio)))
     return out

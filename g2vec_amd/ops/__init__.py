@@ -424,3 +424,59 @@ def perm_t_counts(expr, masks, stat_obs, moments=None):
                                 maxstat)
         return counts, maxstat
     return cpu_ref.perm_t_counts(expr, masks, n1, stat_obs)
+
+
+# ------------------------------------------------------------------ nearest genes
+def knn_topk(Xq, X, k: int, q_index=None, grid_y: int = 0):
+    """(idx i32 [Q, k], val f32 [Q, k]): for every row of Xq f32 [Q, h] the k
+    largest dot(Xq[q], X[g]) over the rows g != q_index[q] of X f32 [G, h]
+    (q_index i32 [Q]; -1 or None excludes nothing). Total order: value
+    descending, equal values (-0.0 == +0.0) by ascending g; with fewer than
+    k candidates the tail is idx -1, val -inf. 1 <= k <= 64, inputs finite.
+    A function of the inputs only: bitwise equal run to run and for every
+    grid_y (GPU launch split over the candidates; 0 = automatic). Widths
+    that are no multiple of 4 are zero-padded (exact) on the GPU."""
+    for name, t in (("Xq", Xq), ("X", X)):
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError(f"{name} must be a float32 [rows, h] tensor")
+    if Xq.shape[1] != X.shape[1]:
+        raise ValueError(f"Xq has {Xq.shape[1]} columns, X has {X.shape[1]}")
+    if X.device != Xq.device:
+        raise ValueError("Xq and X must be on the same device")
+    if not 1 <= int(k) <= 64:
+        raise ValueError(f"k must be in [1, 64], got {k}")
+    if X.shape[0] >= 2 ** 31:
+        raise ValueError("X must have fewer than 2^31 rows")
+    if grid_y < 0:
+        raise ValueError("grid_y must be >= 0")
+    # NaN has no place in a total order
+    if not (bool(torch.isfinite(Xq).all()) and bool(torch.isfinite(X).all())):
+        raise ValueError("Xq and X must be finite")
+    Q, G = Xq.shape[0], X.shape[0]
+    if q_index is not None:
+        if q_index.dim() != 1 or q_index.shape[0] != Q or \
+                q_index.dtype not in (torch.int32, torch.int64):
+            raise ValueError("q_index must be an int32/int64 [Q] tensor")
+        if q_index.device != Xq.device:
+            raise ValueError("q_index must be on Xq's device")
+        q_index = q_index.int().contiguous()
+    if not Xq.is_cuda:
+        return cpu_ref.knn_topk(Xq, X, int(k), q_index)
+    nat = native()
+    pad = -X.shape[1] % 4
+    if pad or X.shape[1] == 0:
+        pad = pad or 4
+        Xq = torch.nn.functional.pad(Xq, (0, pad))
+        X = torch.nn.functional.pad(X, (0, pad))
+    Xq, X = Xq.contiguous(), X.contiguous()
+    idx = torch.empty(Q, k, dtype=torch.int32, device=Xq.device)
+    val = torch.empty(Q, k, dtype=torch.float32, device=Xq.device)
+    gy = nat.knn_grid_y(Q, G, int(grid_y))
+    part_idx = part_val = None
+    if gy > 1:
+        part_idx = torch.empty(Q, gy, k, dtype=torch.int32, device=Xq.device)
+        part_val = torch.empty(Q, gy, k, dtype=torch.float32,
+                               device=Xq.device)
+    nat.knn_topk_(Xq, X, q_index, int(k), int(grid_y), part_idx, part_val,
+                  idx, val)
+    return idx, val

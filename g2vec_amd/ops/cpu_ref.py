@@ -384,3 +384,50 @@ def perm_t_counts(expr: torch.Tensor, masks: torch.Tensor, n1: int,
         if G > 0:
             maxstat[lo:lo + blk] = st.max(dim=1).values
     return counts.int(), maxstat
+
+
+# --------------------------------------------------------------- nearest genes
+KNN_QB = 64        # query rows per matmul call (zero-padded to it)
+KNN_CB = 4096      # candidate rows per matmul call
+
+
+def knn_topk(Xq: torch.Tensor, X: torch.Tensor, k: int,
+             q_index=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(idx i32 [Q, k], val f32 [Q, k]) of knn_tile_kernel: f32 matmul in
+    candidate blocks (nothing of size Q x G is held), the self index masked
+    to -inf, and a stable sort on -val, so equal values keep the lower
+    candidate index (-0.0 and +0.0 tie). Missing tail: idx -1, val -inf.
+    Every matmul call is KNN_QB query rows (the last block zero-padded)
+    against KNN_CB candidates, whatever Q is: a BLAS may block a product by
+    its shape, and a query's scores must not depend on how many others
+    were asked with it."""
+    Q, G, h = Xq.shape[0], X.shape[0], Xq.shape[1]
+    ninf = float("-inf")
+    out_val = torch.full((Q, k), ninf, dtype=torch.float32)
+    out_idx = torch.full((Q, k), -1, dtype=torch.int64)
+    rows = torch.arange(KNN_QB)
+    for q0 in range(0, Q, KNN_QB):
+        n = min(KNN_QB, Q - q0)
+        xq = torch.zeros(KNN_QB, h, dtype=torch.float32)
+        xq[:n] = Xq[q0:q0 + n]
+        qi = torch.full((KNN_QB,), -1, dtype=torch.int64)
+        if q_index is not None:
+            qi[:n] = q_index[q0:q0 + n].long()
+        val = torch.full((KNN_QB, k), ninf, dtype=torch.float32)
+        idx = torch.full((KNN_QB, k), -1, dtype=torch.int64)
+        for lo in range(0, G, KNN_CB):
+            hi = min(G, lo + KNN_CB)
+            sc = xq @ X[lo:hi].t()
+            hit = (qi >= lo) & (qi < hi)
+            sc[rows[hit], qi[hit] - lo] = ninf
+            # kept entries come first and hold lower indices than the block's
+            v = torch.cat([val, sc], dim=1)
+            i = torch.cat([idx, torch.arange(lo, hi).expand(KNN_QB, hi - lo)],
+                          dim=1)
+            order = torch.sort(-v, dim=1, stable=True).indices[:, :k]
+            val = torch.gather(v, 1, order)
+            idx = torch.gather(i, 1, order)
+        out_val[q0:q0 + n] = val[:n]
+        out_idx[q0:q0 + n] = idx[:n]
+    out_idx[out_val == ninf] = -1
+    return out_idx.int(), out_val

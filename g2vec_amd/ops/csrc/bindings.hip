@@ -782,6 +782,106 @@ void perm_t_counts_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
   LAUNCH_CHECK();
 }
 
+// ------------------------------------------- nearest genes: MFMA GEMM + top-k
+// The launch split of knn_topk_: each block walks its share of the candidate
+// tiles against one query tile, never more blocks along y than candidate
+// tiles. The target is the number of blocks the device holds at once (CUs x
+// the kernel's resident blocks per CU), not the ~2048 of perm_t_check: a
+// block starts with empty lists and pays ~k ln(tiles * 64 / k) inserts per
+// row however long its walk is, so fewer, longer walks amortize them, and a
+// single resident set has no tail (100 x 1M x 512: 2.13 ms at 512 blocks
+// against 3.38 ms at 2048 and 2.74 ms at 256). grid_y > 0 forces the split
+// (tests).
+int64_t knn_grid_y(int64_t Q, int64_t G, int64_t grid_y) {
+  TORCH_CHECK(Q >= 0 && G >= 0 && grid_y >= 0,
+              "knn_grid_y: negative argument");
+  const long long nqt = (Q + KN_TILE - 1) / KN_TILE;
+  const long long nct = (G + KN_TILE - 1) / KN_TILE;
+  long long gy = grid_y;
+  if (gy == 0) {
+    int n_cu = 0, per_cu = 0, dev = 0;
+    TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
+                    hipDeviceGetAttribute(
+                        &n_cu, hipDeviceAttributeMultiprocessorCount, dev) ==
+                        hipSuccess &&
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                        &per_cu, knn_tile_kernel, 256, 0) == hipSuccess &&
+                    n_cu >= 1 && per_cu >= 1,
+                "knn_grid_y: cannot read the device's CU count and the "
+                "kernel's occupancy");
+    const long long resident = (long long)n_cu * per_cu;
+    gy = nqt > 0 ? (resident + nqt - 1) / nqt : 1;
+  }
+  if (gy > nct) gy = nct;
+  if (gy > 65535) gy = 65535;
+  if (gy < 1) gy = 1;
+  return gy;
+}
+
+void knn_topk_(torch::Tensor Xq, torch::Tensor X,
+               std::optional<torch::Tensor> q_index, int64_t k,
+               int64_t grid_y, std::optional<torch::Tensor> part_idx,
+               std::optional<torch::Tensor> part_val, torch::Tensor idx,
+               torch::Tensor val) {
+  // every guard runs before the first launch: a refused call leaves idx and
+  // val as they were
+  CHECK_F32(Xq); CHECK_F32(X); CHECK_I32(idx); CHECK_F32(val);
+  TORCH_CHECK(Xq.dim() == 2 && X.dim() == 2,
+              "Xq must be [Q, h] and X [G, h]");
+  const long long Q = Xq.size(0), G = X.size(0), h = X.size(1);
+  TORCH_CHECK(Xq.size(1) == h, "Xq has ", Xq.size(1), " columns, X has ", h);
+  TORCH_CHECK(h >= 4 && h % 4 == 0 && h < (1LL << 31),
+              "knn_topk: h must be a positive multiple of 4, got ", h);
+  CHECK_ROWS16(Xq); CHECK_ROWS16(X);
+  TORCH_CHECK(k >= 1 && k <= 64, "knn_topk: k must be in [1, 64], got ", k);
+  TORCH_CHECK(G < (1LL << 31), "knn_topk: G must be below 2^31");
+  TORCH_CHECK(X.device() == Xq.device() && idx.device() == Xq.device() &&
+                  val.device() == Xq.device(),
+              "knn_topk: all tensors must be on one device");
+  if (q_index) {
+    CHECK_I32(*q_index);
+    TORCH_CHECK(q_index->dim() == 1 && q_index->numel() == Q,
+                "q_index must be [Q]");
+    TORCH_CHECK(q_index->device() == Xq.device(),
+                "knn_topk: all tensors must be on one device");
+  }
+  TORCH_CHECK(idx.dim() == 2 && idx.size(0) == Q && idx.size(1) == k &&
+                  val.dim() == 2 && val.size(0) == Q && val.size(1) == k,
+              "idx and val must be [Q, k]");
+  TORCH_CHECK(grid_y >= 0, "grid_y must be >= 0 (0 = automatic)");
+  const long long gy = knn_grid_y(Q, G, grid_y);
+  const long long nqt = (Q + KN_TILE - 1) / KN_TILE;
+  TORCH_CHECK(nqt < (1LL << 31), "knn_topk: too many queries");
+  if (gy > 1) {
+    TORCH_CHECK(part_idx.has_value() && part_val.has_value(),
+                "knn_topk: a split over ", gy,
+                " blocks needs the partial buffers");
+    CHECK_I32(*part_idx); CHECK_F32(*part_val);
+    TORCH_CHECK(part_idx->numel() == Q * gy * k &&
+                    part_val->numel() == Q * gy * k,
+                "part_idx and part_val must be [Q, ", gy, ", k]");
+    TORCH_CHECK(part_idx->device() == Xq.device() &&
+                    part_val->device() == Xq.device(),
+                "knn_topk: all tensors must be on one device");
+  }
+  check_gfx950("knn_topk");
+  if (Q == 0) return;
+  const int* qi = q_index ? q_index->data_ptr<int>() : nullptr;
+  hipLaunchKernelGGL(
+      knn_tile_kernel, dim3((unsigned)nqt, (unsigned)gy), dim3(256), 0,
+      cur_stream(), Xq.data_ptr<float>(), X.data_ptr<float>(), qi, Q, G,
+      (int)h, (int)k, gy > 1 ? part_idx->data_ptr<int>() : idx.data_ptr<int>(),
+      gy > 1 ? part_val->data_ptr<float>() : val.data_ptr<float>());
+  LAUNCH_CHECK();
+  if (gy > 1) {
+    hipLaunchKernelGGL(knn_merge_kernel, dim3(grid_for(Q, 4)), dim3(256), 0,
+                       cur_stream(), part_idx->data_ptr<int>(),
+                       part_val->data_ptr<float>(), Q, (int)gy, (int)k,
+                       idx.data_ptr<int>(), val.data_ptr<float>());
+    LAUNCH_CHECK();
+  }
+}
+
 // ------------------------------------------------- native host TSV parser
 std::tuple<std::vector<std::string>, std::vector<std::string>, torch::Tensor>
 parse_expression_tsv(const std::string& path) {
@@ -910,6 +1010,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "t^2 per (relabelling, gene), MFMA f32 (out-arg)");
   m.def("perm_t_counts_", &perm_t_counts_,
         "per-gene exceed counts + per-relabelling max t^2 (out-args)");
+  m.def("knn_grid_y", &knn_grid_y, py::arg("Q"), py::arg("G"),
+        py::arg("grid_y") = 0, "candidate-split block count of knn_topk_");
+  m.def("knn_topk_", &knn_topk_, py::arg("Xq"), py::arg("X"),
+        py::arg("q_index"), py::arg("k"), py::arg("grid_y"),
+        py::arg("part_idx"), py::arg("part_val"), py::arg("idx"),
+        py::arg("val"),
+        "k largest dots per query row, MFMA f32 + fused top-k (out-args)");
   m.def("parse_expression_tsv", &parse_expression_tsv,
         "native expression TSV parser");
 }

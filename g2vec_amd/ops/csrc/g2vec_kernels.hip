@@ -1605,3 +1605,238 @@ perm_t_counts_kernel(const float* __restrict__ expr,
   perm_t_body(expr, masks, T, Q, stat_obs, S, G, B, n1, nullptr, counts,
               maxstat);
 }
+
+// ===================================== nearest genes: fused MFMA GEMM + top-k
+// For every query row q of Xq f32[Q, h]: the k candidates g of X f32[G, h]
+// with the largest dot(Xq[q], X[g]), g != q_index[q], in the TOTAL order
+// "value descending, equal values by ascending candidate index" (-0.0 ==
+// +0.0 is a tie). The dot is the MFMA's k-ordered f32 chain. Nothing of size
+// Q x G is written: a score tile lives in LDS just long enough to be
+// compared with each row's current k-th entry.
+//
+// The selection keeps a row's sorted list one entry per lane of a wave
+// (k <= 64; all 64 lanes hold entries, the first k are the result). Empty
+// entries are (-inf, KN_EMPTY): every real candidate is ahead of them. As
+// the order is total and candidate indices are distinct, the top k of a set
+// do not depend on the order of the inserts or on how the candidates were
+// split over blocks: results are bitwise equal for every launch split.
+#define KN_TILE 64                 // queries x candidates per block and tile
+#define KN_KC 64                   // columns of h per LDS-staged K chunk
+#define KN_LD (KN_KC + 2)          // operand tiles [row][k]: stride = 2 mod 32
+#define KN_LDS (KN_TILE + 4)       // score tile [query][cand]: 4 rows = 16 mod 32
+#define KN_NLD (KN_TILE * KN_KC / 4 / 256)   // staged float4 per thread and tile
+#define KN_EMPTY 0x7fffffff
+
+__device__ __forceinline__ bool knn_ahead(float av, int ai, float bv, int bi) {
+  return av > bv || (av == bv && ai < bi);
+}
+
+// The value a wave-uniform lane l holds: v_readlane_b32, no trip through
+// the LDS crossbar as __shfl (ds_bpermute) takes.
+__device__ __forceinline__ int knn_lane(int v, int l) {
+  return __builtin_amdgcn_readlane(v, l);
+}
+__device__ __forceinline__ float knn_lane(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+// Offer every lane's candidate (v, g), live where pend, to the list
+// (lv, li). A ballot of zero against the k-th entry is the common case; the
+// survivors go in one at a time: position = number of entries ahead of the
+// candidate (a prefix, the list is sorted), entries behind it move up a lane.
+__device__ __forceinline__ void knn_insert(float& lv, int& li, float v, int g,
+                                           bool pend, int k, int lane) {
+  float tv = knn_lane(lv, k - 1);
+  int ti = knn_lane(li, k - 1);
+  pend = pend && knn_ahead(v, g, tv, ti);
+  unsigned long long m = __ballot(pend);
+  while (m) {
+    const int b = __ffsll(m) - 1;
+    const float cv = knn_lane(v, b);
+    const int cg = knn_lane(g, b);
+    const int p = __popcll(__ballot(knn_ahead(lv, li, cv, cg)));
+    const float uv = __shfl_up(lv, 1);
+    const int ui = __shfl_up(li, 1);
+    if (lane == p) {
+      lv = cv;
+      li = cg;
+    } else if (lane > p) {
+      lv = uv;
+      li = ui;
+    }
+    tv = knn_lane(lv, k - 1);
+    ti = knn_lane(li, k - 1);
+    pend = pend && lane != b && knn_ahead(v, g, tv, ti);
+    m = __ballot(pend);
+  }
+}
+
+// 64 queries (blockIdx.x) against the candidate tiles blockIdx.y,
+// +gridDim.y, ...; wave w owns the 32x32 sub-tile (w>>1, w&1) as 2x2
+// fragments of v_mfma_f32_16x16x4_f32, A = queries, B = candidates (both
+// rows x K with K contiguous: the stage is 16-byte loads, 16 lanes per row).
+// K runs over h in KN_KC chunks, zero-filled past h; the loads of the next
+// chunk (or of the next tile's first) are issued into registers before the
+// MFMA loop and land in LDS after it. After a tile's last chunk the scores
+// go to LDS over the dead operand tiles and wave w selects for query rows
+// 16w .. 16w+15, one candidate per lane.
+// out_idx / out_val are [Q, gridDim.y, k]: the final result when
+// gridDim.y == 1, else the partial lists knn_merge_kernel folds.
+extern "C" __global__ void __launch_bounds__(256)
+knn_tile_kernel(const float* __restrict__ Xq, const float* __restrict__ X,
+                const int* __restrict__ q_index, long long Q, long long G,
+                int h, int k, int* __restrict__ out_idx,
+                float* __restrict__ out_val) {
+#if defined(__gfx950__)
+  __shared__ __attribute__((aligned(16))) float lds[2 * KN_TILE * KN_LD];
+  float* As = lds;
+  float* Bs = lds + KN_TILE * KN_LD;
+  float* Sc = lds;                             // [64][KN_LDS] <= both tiles
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1;
+  const int fr = lane & 15, kk = lane >> 4;
+  const long long q0 = (long long)blockIdx.x * KN_TILE;
+
+  // lane r < 16 holds the excluded candidate of query row 16 * wid + r
+  int self_r = -1;
+  if (q_index && lane < 16 && q0 + 16 * wid + lane < Q)
+    self_r = q_index[q0 + 16 * wid + lane];
+
+  float lv[16];
+  int li[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    lv[r] = -INFINITY;
+    li[r] = KN_EMPTY;
+  }
+
+  // staging registers: float4 (row, c4) = (16 * i + tid / 16, tid % 16) of
+  // the 64 x 64 chunk of either operand. h % 4 == 0, so a float4 lies
+  // entirely inside a row or entirely past it.
+  f32x4 ar[KN_NLD], br[KN_NLD];
+  const int srow = threadIdx.x >> 4, sc4 = (threadIdx.x & 15) * 4;
+  auto prefetch = [&](long long pc0, int pk0) {
+#pragma unroll
+    for (int i = 0; i < KN_NLD; ++i) {
+      const int row = 16 * i + srow;
+      const bool kin = pk0 + sc4 < h;
+      ar[i] = (kin && q0 + row < Q)
+          ? *(const f32x4*)(Xq + (q0 + row) * h + pk0 + sc4) : (f32x4)(0.f);
+      br[i] = (kin && pc0 + row < G)
+          ? *(const f32x4*)(X + (pc0 + row) * h + pk0 + sc4) : (f32x4)(0.f);
+    }
+  };
+
+  const long long nct = (G + KN_TILE - 1) / KN_TILE;
+  if ((long long)blockIdx.y < nct) prefetch((long long)blockIdx.y * KN_TILE, 0);
+  for (long long ct = blockIdx.y; ct < nct; ct += gridDim.y) {
+    const long long c0 = ct * KN_TILE;
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4)(0.f);
+
+    for (int k0 = 0; k0 < h; k0 += KN_KC) {
+      const int kc = (h - k0 < KN_KC) ? h - k0 : KN_KC;    // multiple of 4
+      __syncthreads();          // readers of the last chunk / score tile done
+#pragma unroll
+      for (int i = 0; i < KN_NLD; ++i) {
+        float* pa = As + (16 * i + srow) * KN_LD + sc4;    // 8-byte aligned
+        float* pb = Bs + (16 * i + srow) * KN_LD + sc4;
+        pa[0] = ar[i][0]; pa[1] = ar[i][1]; pa[2] = ar[i][2]; pa[3] = ar[i][3];
+        pb[0] = br[i][0]; pb[1] = br[i][1]; pb[2] = br[i][2]; pb[3] = br[i][3];
+      }
+      __syncthreads();
+      if (k0 + KN_KC < h)
+        prefetch(c0, k0 + KN_KC);
+      else if (ct + gridDim.y < nct)
+        prefetch((ct + gridDim.y) * KN_TILE, 0);
+      for (int kq = 0; kq < kc; kq += 4) {
+        float av[2], bv[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+          av[a] = As[(wr * 32 + a * 16 + fr) * KN_LD + kq + kk];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+          bv[b] = Bs[(wc * 32 + b * 16 + fr) * KN_LD + kq + kk];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                av[a], bv[b], acc[a][b], 0, 0, 0);
+      }
+    }
+
+    // C/D map (16x16): col = lane&15 (candidate), row = (lane>>4)*4 + reg
+    // (query). Padded rows and candidates are computed and masked below.
+    __syncthreads();                     // operand tiles dead in every wave
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+          Sc[(wr * 32 + a * 16 + kk * 4 + reg) * KN_LDS + wc * 32 + b * 16 +
+             fr] = acc[a][b][reg];
+    __syncthreads();
+
+    const long long g = c0 + lane;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = 16 * wid + r;
+      const int self = knn_lane(self_r, r);
+      const bool live = q0 + row < Q && g < G && g != (long long)self;
+      knn_insert(lv[r], li[r], Sc[row * KN_LDS + lane], (int)g, live, k, lane);
+    }
+  }
+
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const long long q = q0 + 16 * wid + r;
+    if (q < Q && lane < k) {
+      const long long o = (q * gridDim.y + blockIdx.y) * k + lane;
+      out_idx[o] = li[r] == KN_EMPTY ? -1 : li[r];
+      out_val[o] = lv[r];
+    }
+  }
+#endif
+}
+
+// One wave per query: fold its gy partial lists [Q, gy, k] into idx / val
+// [Q, k] with the insert routine of the tile kernel (empty entries carry
+// index -1 and are skipped).
+extern "C" __global__ void __launch_bounds__(256)
+knn_merge_kernel(const int* __restrict__ part_idx,
+                 const float* __restrict__ part_val, long long Q, int gy,
+                 int k, int* __restrict__ idx, float* __restrict__ val) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  for (long long q = (long long)blockIdx.x * 4 + wid; q < Q;
+       q += (long long)gridDim.x * 4) {
+    float lv = -INFINITY;
+    int li = KN_EMPTY;
+    // the query's gy lists are one contiguous run of gy * k entries: 64 at
+    // a time, whatever k is, the next 64 loaded before the current insert
+    const long long n = (long long)gy * k;
+    const int* pi = part_idx + q * n;
+    const float* pv = part_val + q * n;
+    int g = lane < n ? pi[lane] : -1;
+    float v = lane < n ? pv[lane] : 0.f;
+    for (long long e0 = 0; e0 < n; e0 += WAVE) {
+      const long long e = e0 + WAVE + lane;
+      const int g_next = e < n ? pi[e] : -1;
+      const float v_next = e < n ? pv[e] : 0.f;
+      knn_insert(lv, li, v, g, g >= 0, k, lane);
+      g = g_next;
+      v = v_next;
+    }
+    if (lane < k) {
+      idx[q * k + lane] = li == KN_EMPTY ? -1 : li;
+      val[q * k + lane] = lv;
+    }
+  }
+}

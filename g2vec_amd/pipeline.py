@@ -245,6 +245,21 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
         jsonl.emit("perm", B=cfg.permutations, seed=perm_seed,
                    seconds=time.perf_counter() - t0,
                    n_q05=int(np.sum(perm["q_bh"] <= 0.05)))
+    nbr = None
+    if cfg.neighbors > 0:
+        from .neighbors import nearest_genes
+        if cfg.neighbors_of == "all":
+            nbr_q = np.arange(n_genes, dtype=np.int64)
+        else:
+            row_of = {str(g): i for i, g in enumerate(data["gene"])}
+            nbr_q = np.array([row_of[str(b)] for b in biomarkers],
+                             dtype=np.int64)
+        t0 = time.perf_counter()
+        with timers.phase("neighbors"):
+            nbr = nearest_genes(W_dev if W_dev is not None else W, nbr_q,
+                                cfg.neighbors, metric="cosine", device=device)
+        jsonl.emit("neighbors", Q=int(nbr_q.size), k=cfg.neighbors,
+                   seconds=time.perf_counter() - t0)
 
     log(">>> 7. Save results")
     with timers.phase("write"):
@@ -258,6 +273,10 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
             f4 = gio.write_scores(cfg.result_name, data["gene"], lg, scores,
                                   perm)
             log("    %s" % f4)
+        if nbr is not None:
+            f5 = gio.write_neighbors(cfg.result_name, data["gene"], nbr_q,
+                                     nbr[0], nbr[1], lg, biomarkers)
+            log("    %s" % f5)
 
     result.update({"lgroups": lg, "biomarkers": biomarkers,
                    "timers": timers.summary()})
