@@ -443,6 +443,21 @@ cbow_fwd_scalar_kernel(const float* __restrict__ s, const int* __restrict__ gene
 // accumulation order — is the same code, hence bitwise-equal outputs.
 // subs_per_block = blockDim.x / SUBW is read by the entry point: only in a
 // __global__ function does the compiler fold blockDim to one scalar load.
+//
+// The gather is latency-bound (id load -> dependent s load, ~0.7 TB/s of
+// id traffic at the ex shape), so a path is walked in ROUNDS of EVAL_U x 16
+// instances: EVAL_U independent nontemporal id loads back to back, then
+// EVAL_U gathers, then the adds — in ascending i per lane, the exact
+// sequence of `partial += st[genes[i]]` (cbow_fwd_scalar_kernel defines
+// that order). A slot past hi re-loads the path's last id (in range) and
+// is dropped by a select, never by adding 0.0f (-0.0f must survive). The
+// next path's offs/label loads are issued ahead of the current path's
+// rounds. An empty path runs no round: no id load, no gather.
+// EVAL_U = 5 covers len_path 80 in one round (registers: docs/KERNELS.md).
+#ifndef EVAL_U
+#define EVAL_U 5
+#endif
+
 __device__ __forceinline__ void
 eval_counts_body(const float* __restrict__ st, const int* __restrict__ genes,
                  const int* __restrict__ offs, const float* __restrict__ labels,
@@ -450,16 +465,37 @@ eval_counts_body(const float* __restrict__ st, const int* __restrict__ genes,
                  float* __restrict__ dO, float inv_b, int subs_per_block) {
   const int sublane = threadIdx.x & (SUBW - 1);
   const int sub = threadIdx.x / SUBW;
+  const long long stride = (long long)gridDim.x * subs_per_block;
   float c0 = 0.f, c1 = 0.f;                    // sublane-0 accumulators
-  for (long long p = (long long)blockIdx.x * subs_per_block + sub; p < P;
-       p += (long long)gridDim.x * subs_per_block) {
-    const int lo = offs[p], hi = offs[p + 1];
+  long long p = (long long)blockIdx.x * subs_per_block + sub;
+  int lo = 0, hi = 0;
+  float y = 0.f;
+  if (p < P) { lo = offs[p]; hi = offs[p + 1]; y = labels[p]; }
+  while (p < P) {
+    const long long pn = p + stride;
+    // next path's bounds + label, in flight during this path's rounds.
+    // Unconditional (index clamped to the last path): behind a branch the
+    // compiler's wait for lo/hi below would also wait for these loads.
+    const long long pc = pn < P ? pn : P - 1;
+    const int lo_n = offs[pc], hi_n = offs[pc + 1];
+    const float y_n = labels[pc];
     float partial = 0.f;
-    for (int i = lo + sublane; i < hi; i += SUBW)
-      partial += st[__builtin_nontemporal_load(&genes[i])];
+    for (int i0 = lo + sublane; i0 - sublane < hi; i0 += EVAL_U * SUBW) {
+      int id[EVAL_U];
+      float sv[EVAL_U];
+#pragma unroll
+      for (int u = 0; u < EVAL_U; ++u) {
+        const int i = i0 + u * SUBW;
+        id[u] = __builtin_nontemporal_load(&genes[i < hi ? i : hi - 1]);
+      }
+#pragma unroll
+      for (int u = 0; u < EVAL_U; ++u) sv[u] = st[id[u]];
+#pragma unroll
+      for (int u = 0; u < EVAL_U; ++u)
+        partial = (i0 + u * SUBW < hi) ? partial + sv[u] : partial;
+    }
     const float o = subwave_sum16(partial);
     if (sublane == 0) {
-      const float y = labels[p];
       const float corr = is_correct(o, y);
       if (p < p_split) c0 += corr; else c1 += corr;
       // fused next-epoch forward: this eval's s IS the next epoch's
@@ -468,6 +504,7 @@ eval_counts_body(const float* __restrict__ st, const int* __restrict__ genes,
       // over the train paths runs ONCE per weight version, not twice)
       if (dO && p < p_split) dO[p] = dlogit(o, y, inv_b);
     }
+    p = pn; lo = lo_n; hi = hi_n; y = y_n;
   }
   block_fold2(c0, c1, partials + 2 * blockIdx.x);
 }
