@@ -96,6 +96,13 @@ def build_parser() -> argparse.ArgumentParser:
                    default="biomarkers",
                    help="query genes of --neighbors: the selected biomarkers "
                         "or every gene")
+    p.add_argument("--replicates", type=int, default=1, metavar="R",
+                   help="train R models that differ only in their initial "
+                        "weights (seed, seed+1, ...) in one batched epoch; "
+                        "the standard outputs stay replica 0's, and "
+                        "RESULT_NAME_stability.txt and "
+                        "RESULT_NAME_consensus_biomarkers.txt report which "
+                        "genes survive the change of seed (1..32; 1 = off)")
     p.add_argument("--save-paths", type=str, default="")
     p.add_argument("--load-model", type=str, default="",
                    help="skip training: load W_ih from a --save-model .pt "
@@ -130,7 +137,8 @@ def args_to_config(a: argparse.Namespace) -> G2VecConfig:
         use_hipgraph=not a.no_hipgraph,
         write_scores=a.write_scores or a.permutations > 0,
         permutations=a.permutations, perm_seed=a.perm_seed,
-        neighbors=a.neighbors, neighbors_of=a.neighbors_of)
+        neighbors=a.neighbors, neighbors_of=a.neighbors_of,
+        replicates=a.replicates)
 
 
 def main(argv=None) -> int:

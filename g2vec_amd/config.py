@@ -101,6 +101,41 @@ class G2VecConfig:
                                     # of every query gene (neighbors.py)
     neighbors_of: str = "biomarkers"  # query set: "biomarkers" (file order)
                                     # | "all" (every gene, gene order)
+    # repr=False: the ">>> 0. Arguments" line of a run without the flag stays
+    # as it was; a run with it reports R under step 4
+    replicates: int = dataclasses.field(default=1, repr=False)
+                                    # R > 1: train R models that differ only
+                                    # in their initial weights (replica r =
+                                    # seed + r) in one batched epoch, run
+                                    # steps 5-6 per replica and write the
+                                    # stability table + consensus biomarkers
+                                    # (models/replicas.py, stability.py);
+                                    # 1 = off
+
+    def check_replicate_scope(self) -> None:
+        """The batched trainer covers the default training regime only; any
+        other option is an error that names it, never a silent no-op."""
+        bad = None
+        if self.trainer_path != "fast":
+            bad = f"trainer_path={self.trainer_path}"
+        elif self.batch_size != 0:
+            bad = f"batch_size={self.batch_size}"
+        elif self.dtype != "fp32":
+            bad = f"dtype={self.dtype}"
+        elif self.activation != "none":
+            bad = f"activation={self.activation}"
+        elif self.earlystop_every != 1:
+            bad = f"earlystop_every={self.earlystop_every}"
+        elif self.train_ckpt:
+            bad = "train_ckpt"
+        elif self.resume_train:
+            bad = "resume_train"
+        elif self.load_model:
+            bad = "load_model"
+        if bad is not None:
+            raise ValueError(
+                f"replicates > 1 supports the full-batch fp32 fast path with "
+                f"per-epoch early stop only; it conflicts with {bad}")
 
     def validate(self) -> None:
         if self.hidden not in (64, 128, 256, 512, 1024):
@@ -154,6 +189,10 @@ class G2VecConfig:
             raise ValueError("neighbors must be in [0, 64] (0 = off)")
         if self.neighbors_of not in ("biomarkers", "all"):
             raise ValueError(f"bad neighbors_of {self.neighbors_of}")
+        if not 1 <= self.replicates <= 32:
+            raise ValueError("replicates must be in [1, 32] (1 = off)")
+        if self.replicates > 1:
+            self.check_replicate_scope()
 
 
 def resolve_device(device: str) -> str:

@@ -89,6 +89,36 @@ def write_scores(result_name: str, genes: Sequence[str],
     return out
 
 
+def write_stability(result_name: str, genes: Sequence[str],
+                    summary: dict) -> str:
+    """<name>_stability.txt from stability.summarize: one tab-separated row
+    per gene, in gene order. Columns GeneSymbol, Lgroup (replica 0's),
+    LgroupMode, LgroupAgreement (%.4f), Selected (replicas whose biomarker
+    list holds the gene), Frequency (Selected / R, %.4f), MeanGeneScore
+    (%.6f, NA if no replica defines one)."""
+    out = result_name + "_stability.txt"
+    mgs = np.asarray(summary["mean_gene_score"], dtype=np.float64)
+    with open(out, "w") as f:
+        f.write("GeneSymbol\tLgroup\tLgroupMode\tLgroupAgreement\tSelected\t"
+                "Frequency\tMeanGeneScore\n")
+        for i, gene in enumerate(genes):
+            f.write("%s\t%d\t%d\t%.4f\t%d\t%.4f\t%s\n" % (
+                gene, int(summary["lgroup"][i]),
+                int(summary["lgroup_mode"][i]),
+                float(summary["lgroup_agreement"][i]),
+                int(summary["selected"][i]), float(summary["frequency"][i]),
+                "NA" if np.isnan(mgs[i]) else "%.6f" % mgs[i]))
+    return out
+
+
+def write_consensus(result_name: str, genes: Sequence[str],
+                    summary: dict) -> str:
+    """<name>_consensus_biomarkers.txt: the consensus genes of
+    stability.summarize, most stable first, in the biomarker file format."""
+    return write_biomarkers(result_name + "_consensus",
+                            [str(genes[int(i)]) for i in summary["consensus"]])
+
+
 def write_neighbors(result_name: str, genes: Sequence[str],
                     queries: Sequence[int], idx: np.ndarray, sim: np.ndarray,
                     lgroup_idx: Sequence[int],

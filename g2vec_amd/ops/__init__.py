@@ -282,6 +282,110 @@ def gemv_cols(W, c, out) -> None:
     torch.mv(W.t(), c, out=out)
 
 
+# ------------------------------------------------------------------ replica-batched fast path
+# R independently initialised models over ONE path set (models/replicas.py).
+# Layouts, all f32 and contiguous: s_R / c_R [G, R] and dO_R [P_tr, R]
+# replica-minor, counts_R [R, 2], W/m/v [R, G, h] and who/mO/vO [R, h]
+# replica-major (W[r] is an ordinary [G, h] view). Contract: for every
+# replica r each output is bitwise what the single op above gives on the same
+# device when fed replica r's slice. The CPU mirrors loop the single ops.
+REP_MAX = 32
+
+
+def _rep_R(t: torch.Tensor, name: str) -> int:
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 [rows, R] tensor")
+    R = int(t.shape[1])
+    if not 1 <= R <= REP_MAX:
+        raise ValueError(f"{name}: R must be in [1, {REP_MAX}], got {R}")
+    return R
+
+
+def cbow_eval_counts_rep_(s_R, genes, offsets, labels, p_split: int,
+                          counts_R: torch.Tensor,
+                          dO_R: Optional[torch.Tensor] = None,
+                          inv_b: float = 1.0) -> None:
+    """Batched cbow_eval_counts_: counts_R[r] = the two correct counts of
+    replica r (OVERWRITTEN, no zeroing needed) and, with dO_R, column r of
+    dO_R[:p_split] = its train-split dlogits. Rows of dO_R at or beyond
+    p_split are not written."""
+    R = _rep_R(s_R, "s_R")
+    if s_R.is_cuda:
+        native().cbow_eval_counts_rep_(s_R, genes, offsets, labels,
+                                       int(p_split), counts_R, dO_R=dO_R,
+                                       inv_b=float(inv_b))
+        return
+    for r in range(R):
+        cnt = torch.zeros(2, dtype=torch.float32)
+        d = (torch.empty(p_split, dtype=torch.float32)
+             if dO_R is not None else None)
+        cbow_eval_counts_(s_R[:, r].contiguous(), genes, offsets, labels,
+                          p_split, cnt, dO=d, inv_b=inv_b)
+        counts_R[r] = cnt
+        if dO_R is not None:
+            dO_R[:p_split, r] = d
+
+
+def scatter_dO_rep(plan: ScatterPlan, dO_R, n_genes: int) -> torch.Tensor:
+    """Batched scatter_dO over the single trainer's ScatterPlan: c_R [G, R]
+    with c_R[:, r] = X^T dO_R[:, r]. Slab-blocked plans are driven slab by
+    slab in ascending order, as scatter_dO does (the slab size is the single
+    op's, not re-tuned for the R-times-larger table)."""
+    R = _rep_R(dO_R, "dO_R")
+    c_R = torch.zeros(n_genes, R, dtype=torch.float32, device=dO_R.device)
+    if dO_R.is_cuda:
+        if plan.slab_seg_ptr is None:
+            native().scatter_dO_rep_(plan.inst_path, plan.seg_start,
+                                     plan.seg_gene, dO_R, c_R)
+            return c_R
+        ptr = plan.slab_seg_ptr
+        for a, b in zip(ptr[:-1], ptr[1:]):
+            if b > a:
+                native().scatter_dO_rep_(plan.inst_path,
+                                         plan.seg_start[a:b + 1],
+                                         plan.seg_gene[a:b], dO_R, c_R)
+        return c_R
+    # the plan lists each gene's instances in ascending path order, slab by
+    # slab: the order cpu_ref.scatter_dO adds them in
+    seg_len = (plan.seg_start[1:] - plan.seg_start[:-1]).long()
+    gene_of = torch.repeat_interleave(plan.seg_gene.long(), seg_len)
+    for r in range(R):
+        col = torch.zeros(n_genes, dtype=torch.float32)
+        col.index_add_(0, gene_of, dO_R[:, r][plan.inst_path.long()])
+        c_R[:, r] = col
+    return c_R
+
+
+def adam_rank1_rep(W, m, v, c_R, who, mO, vO, t: int, lr: float, b1: float,
+                   b2: float, eps: float,
+                   lrt_buf: Optional[torch.Tensor] = None) -> None:
+    """Batched adam_rank1_fused. One lr_t for all replicas (they share the
+    Adam step t); lrt_buf as in adam_rank1."""
+    R = _rep_R(c_R, "c_R")
+    if W.dim() != 3 or W.shape[0] != R:
+        raise ValueError("W must be [R, G, h] with R = c_R.shape[1]")
+    if W.is_cuda:
+        lrt_buf = _lrt_buf(lrt_buf, W, t, lr, b1, b2)
+        native().adam_rank1_rep(W, m, v, c_R, who, mO, vO, lrt_buf,
+                                float(b1), float(b2), float(eps))
+        return
+    for r in range(R):
+        adam_rank1_fused(W[r], m[r], v[r], c_R[:, r].contiguous(), who[r],
+                         mO[r], vO[r], t, lr, b1, b2, eps)
+
+
+def gemv_rows_rep_(W, who, s_R) -> None:
+    """s_R[:, r] = W[r] @ who[r]."""
+    R = _rep_R(s_R, "s_R")
+    if W.dim() != 3 or W.shape[0] != R:
+        raise ValueError("W must be [R, G, h] with R = s_R.shape[1]")
+    if W.is_cuda:
+        native().gemv_rows_rep_(W, who, s_R)
+        return
+    for r in range(R):
+        s_R[:, r] = torch.mv(W[r], who[r])
+
+
 # ------------------------------------------------------------------ graph / PCC
 def pcc_edges(zt, edge_idx, n_group: int):
     if zt.is_cuda:

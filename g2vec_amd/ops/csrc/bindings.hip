@@ -522,6 +522,165 @@ void gemv_cols_(torch::Tensor W, torch::Tensor c, torch::Tensor out) {
   LAUNCH_CHECK();
 }
 
+// --------------------------------------------- replica-batched fast path
+// R models over one path set; layouts in g2vec_kernels.hip (REP_MAX). The
+// per-replica launch geometry of every op is the single op's, so the same
+// env caps apply and each replica's output is bitwise the single op's.
+inline int check_rep_table(const torch::Tensor& t, const char* name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.dim() == 2, name, " must be [rows, R]");
+  const long long R = t.size(1);
+  TORCH_CHECK(R >= 1 && R <= REP_MAX, name, ": R must be in [1, ", REP_MAX,
+              "], got ", R);
+  TORCH_CHECK(t.numel() < (1LL << 31), name, " must have < 2^31 elements");
+  return (int)R;
+}
+
+// f(NT, VEC): NT = tiles of four replicas, VEC = 16-byte gathers possible
+template <typename F>
+void dispatch_rep(int R, const void* table, F&& f) {
+  const bool vec = R % 4 == 0 && (reinterpret_cast<uintptr_t>(table) & 15) == 0;
+  auto go = [&](auto NT) {
+    if (vec) f(NT, std::true_type{}); else f(NT, std::false_type{});
+  };
+  switch ((R + 3) / 4) {
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 3: go(std::integral_constant<int, 3>{}); break;
+    case 4: go(std::integral_constant<int, 4>{}); break;
+    case 5: go(std::integral_constant<int, 5>{}); break;
+    case 6: go(std::integral_constant<int, 6>{}); break;
+    case 7: go(std::integral_constant<int, 7>{}); break;
+    default: go(std::integral_constant<int, 8>{}); break;
+  }
+}
+
+void cbow_eval_counts_rep_(torch::Tensor s_R, torch::Tensor genes,
+                           torch::Tensor offs, torch::Tensor labels,
+                           int64_t p_split, torch::Tensor counts_R,
+                           std::optional<torch::Tensor> dO_R, double inv_b) {
+  // counts_R [R, 2] is OVERWRITTEN (the fold writes it); dO_R [>= p_split,
+  // R] receives the train split's dlogits, rows >= p_split stay untouched
+  const int R = check_rep_table(s_R, "s_R");
+  CHECK_I32(genes); CHECK_I32(offs); CHECK_F32(labels); CHECK_F32(counts_R);
+  TORCH_CHECK(counts_R.numel() == 2 * R, "counts_R must be [R, 2]");
+  const long long P = labels.numel();
+  TORCH_CHECK(offs.numel() == P + 1, "offs must have P + 1 elements");
+  TORCH_CHECK(p_split >= 0 && p_split <= P, "p_split must be in [0, P]");
+  if (dO_R) {
+    CHECK_F32(*dO_R);
+    TORCH_CHECK(dO_R->dim() == 2 && dO_R->size(1) == R &&
+                    dO_R->size(0) >= p_split,
+                "dO_R must be [>= p_split, R]");
+  }
+  if (P == 0) return;
+  int grid = grid_for(P, 16);
+  const int gcap = env_int_min1("G2VEC_EVAL_GRID", 2048);
+  if (grid > gcap) grid = gcap;
+  auto partials = torch::empty({grid, R, 2}, opts_on(s_R));
+  float* dOp = dO_R ? dO_R->data_ptr<float>() : nullptr;
+  dispatch_rep(R, s_R.data_ptr<float>(), [&](auto NT, auto VEC) {
+    hipLaunchKernelGGL(
+        (cbow_eval_counts_rep_kernel<decltype(NT)::value,
+                                     decltype(VEC)::value>),
+        dim3(grid), dim3(256), 0, cur_stream(), s_R.data_ptr<float>(),
+        genes.data_ptr<int>(), offs.data_ptr<int>(),
+        labels.data_ptr<float>(), P, (long long)p_split, R,
+        partials.data_ptr<float>(), dOp, (float)inv_b);
+    LAUNCH_CHECK();
+  });
+  hipLaunchKernelGGL(fold_partials_rep_kernel, dim3(R), dim3(256), 0,
+                     cur_stream(), partials.data_ptr<float>(), grid, R,
+                     counts_R.data_ptr<float>());
+  LAUNCH_CHECK();
+}
+
+void scatter_dO_rep_(torch::Tensor inst_path, torch::Tensor seg_start,
+                     torch::Tensor seg_gene, torch::Tensor dO_R,
+                     torch::Tensor c_R) {
+  // accumulating, like scatter_dO_det_: the caller zeroes c_R [G, R] once
+  // and drives slab-blocked plans one slab per call
+  CHECK_I32(inst_path); CHECK_I32(seg_start); CHECK_I32(seg_gene);
+  const int R = check_rep_table(dO_R, "dO_R");
+  TORCH_CHECK(check_rep_table(c_R, "c_R") == R, "c_R and dO_R differ in R");
+  const long long n_seg = seg_gene.numel();
+  if (n_seg == 0) return;
+  TORCH_CHECK(seg_start.numel() == n_seg + 1,
+              "seg_start must have n_seg + 1 elements");
+  // dO_R decides VEC for both tables: c_R rows are written per lane
+  dispatch_rep(R, dO_R.data_ptr<float>(), [&](auto NT, auto VEC) {
+    hipLaunchKernelGGL(
+        (scatter_do_rep_kernel<decltype(NT)::value, decltype(VEC)::value>),
+        dim3(grid_for(n_seg, 4)), dim3(256), 0, cur_stream(),
+        inst_path.data_ptr<int>(), seg_start.data_ptr<int>(),
+        seg_gene.data_ptr<int>(), (int)n_seg, dO_R.data_ptr<float>(), R,
+        c_R.data_ptr<float>());
+    LAUNCH_CHECK();
+  });
+}
+
+void adam_rank1_rep(torch::Tensor W, torch::Tensor m, torch::Tensor v,
+                    torch::Tensor c_R, torch::Tensor who, torch::Tensor mO,
+                    torch::Tensor vO, torch::Tensor lrt, double b1, double b2,
+                    double eps) {
+  // the fused tail of adam_rank1 for W/m/v [R, G, h], who/mO/vO [R, h] and
+  // c_R [G, R]: replica = grid y over the single launch's geometry
+  CHECK_F32(W); CHECK_F32(m); CHECK_F32(v); CHECK_F32(who); CHECK_F32(mO);
+  CHECK_F32(vO);
+  check_lrt(lrt);
+  const int R = check_rep_table(c_R, "c_R");
+  TORCH_CHECK(W.dim() == 3 && W.size(0) == R, "W must be [R, G, h]");
+  const long long G = W.size(1);
+  const int h = (int)W.size(2);
+  TORCH_CHECK(h >= 4 && h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
+              "hidden must be a multiple of 4 with h/4 dividing 256");
+  TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
+              "m/v/W size mismatch");
+  TORCH_CHECK(c_R.size(0) == G, "c_R must have one row per W row");
+  TORCH_CHECK(who.numel() == (long long)R * h && mO.numel() == who.numel() &&
+                  vO.numel() == who.numel(),
+              "who/mO/vO must be [R, h]");
+  if (G == 0) return;
+  const int rpb = 256 / (h / 4);
+  int grid = grid_for(G, rpb);
+  if (grid > 1024) grid = 1024;      // as the single fused launch
+  auto partials = torch::empty({R, grid, h}, opts_on(W));
+  hipLaunchKernelGGL(adam_rank1_rep_kernel, dim3(grid, R), dim3(256), 0,
+                     cur_stream(), W.data_ptr<float>(), m.data_ptr<float>(),
+                     v.data_ptr<float>(), c_R.data_ptr<float>(),
+                     who.data_ptr<float>(), G, h, R, lrt.data_ptr<float>(),
+                     (float)b1, (float)b2, (float)eps,
+                     partials.data_ptr<float>());
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(fold_gw_adam_rep_kernel, dim3(grid_for(h, 4), R),
+                     dim3(256), 0, cur_stream(), partials.data_ptr<float>(),
+                     grid, h, who.data_ptr<float>(), mO.data_ptr<float>(),
+                     vO.data_ptr<float>(), lrt.data_ptr<float>(), (float)b1,
+                     (float)b2, (float)eps);
+  LAUNCH_CHECK();
+}
+
+void gemv_rows_rep_(torch::Tensor W, torch::Tensor who, torch::Tensor s_R) {
+  CHECK_F32(W); CHECK_F32(who);
+  const int R = check_rep_table(s_R, "s_R");
+  TORCH_CHECK(W.dim() == 3 && W.size(0) == R, "W must be [R, G, h]");
+  const long long G = W.size(1);
+  const int h = (int)W.size(2);
+  const int hpl = hpl_for(h);
+  TORCH_CHECK(s_R.size(0) == G && who.numel() == (long long)R * h,
+              "gemv_rows_rep shape mismatch");
+  if (G == 0) return;
+  int grid = grid_for(G, 4);
+  if (grid > 8192) grid = 8192;
+  dispatch_hpl(hpl, [&](auto HPL) {
+    hipLaunchKernelGGL((gemv_rows_rep_kernel<decltype(HPL)::value>),
+                       dim3(grid, R), dim3(256), 0, cur_stream(),
+                       W.data_ptr<float>(), who.data_ptr<float>(), G, h, R,
+                       s_R.data_ptr<float>());
+    LAUNCH_CHECK();
+  });
+}
+
 torch::Tensor bf16_copy(torch::Tensor src) {
   CHECK_F32(src);
   auto out = torch::empty_like(src, src.options().dtype(at::kBFloat16));
@@ -994,6 +1153,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "seeded +-2sigma truncated-normal fill (K9)");
   m.def("gemv_rows_", &gemv_rows_, "s = W @ x (wave-per-row GEMV, out-arg)");
   m.def("gemv_cols_", &gemv_cols_, "out = W^T c (partials + fold, out-arg)");
+  m.def("cbow_eval_counts_rep_", &cbow_eval_counts_rep_,
+        py::arg("s_R"), py::arg("genes"), py::arg("offs"), py::arg("labels"),
+        py::arg("p_split"), py::arg("counts_R"),
+        py::arg("dO_R") = py::none(), py::arg("inv_b") = 1.0,
+        "replica-batched fused eval: counts_R [R, 2] + train dlogits dO_R");
+  m.def("scatter_dO_rep_", &scatter_dO_rep_,
+        "replica-batched deterministic c_R += X^T dO_R (accumulating)");
+  m.def("adam_rank1_rep", &adam_rank1_rep,
+        "replica-batched fused tail: rank-1 Adam + dW_ho fold + who Adam");
+  m.def("gemv_rows_rep_", &gemv_rows_rep_,
+        "s_R[:, r] = W[r] @ who[r] (replica-minor out-arg)");
   m.def("bf16_copy", &bf16_copy, "f32 -> bf16 cast kernel");
   m.def("kmeans_step", &kmeans_step,
         py::arg("X"), py::arg("C"), py::arg("prev"), py::arg("labels"),

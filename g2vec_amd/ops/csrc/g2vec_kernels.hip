@@ -8,6 +8,11 @@
 //   cbow_eval_counts_kernel     fused eval: per-split correct counts + next-epoch train dlogits
 //   cbow_eval_counts_lds_kernel same body with the s table staged in LDS (opt-in)
 //   fold_partials_kernel        one-block fold of [n_blocks, 2] count partials
+//   cbow_eval_counts_rep_kernel<NT,VEC>  the eval body for R replicas (s_R [G, R]): one id load, R gathers
+//   fold_partials_rep_kernel    per-replica fold of its [n_blocks, R, 2] partials
+//   scatter_do_rep_kernel<NT,VEC>  c_R = X^T dO_R over the same plan, replica-minor
+//   adam_rank1_rep_kernel / fold_gw_adam_rep_kernel / gemv_rows_rep_kernel<HPL>
+//                               the fused tail and the GEMV with a replica grid dimension
 //   scatter_do_det_kernel       (K6 collapsed) c = X^T dO by gene-sorted segments, atomic-free
 //   adam_rank1_kernel           (K7) TF1 Adam, rank-1 grad c (x) who; optional dW_ho partials
 //   fold_gw_adam_kernel         folds those partials and applies the W_ho Adam update
@@ -554,6 +559,145 @@ fold_partials_kernel(const float* __restrict__ partials, int n_blocks,
   block_fold2(c0, c1, counts);
 }
 
+// ================================== replica-batched fast path (R <= REP_MAX)
+// R independently initialised models train on ONE path set: ids, offsets,
+// labels and the scatter plan are shared, the tables carry the replica
+// index innermost (s_R [G, R], dO_R [P, R], c_R [G, R]). A kernel handles
+// NT tiles of four replicas: one id load serves all of them and the four
+// values of a tile are one 16-byte gather. VEC = (R % 4 == 0, 16-byte
+// aligned base); otherwise four scalar loads whose replica index is clamped
+// to R - 1 — in range, and the surplus sums are never stored. Per replica
+// every kernel performs the single-model kernel's additions in the
+// single-model kernel's order, so each output is bitwise the single op's.
+#define REP_MAX 32
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <bool VEC>
+__device__ __forceinline__ f32x4 rep_gather4(const float* __restrict__ tab,
+                                             int row, int R, int t) {
+  if (VEC)
+    return ((const f32x4*)tab)[(long long)row * (R >> 2) + t];
+  const float* p = tab + (long long)row * R;
+  f32x4 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int r = 4 * t + k;
+    o[k] = p[r < R ? r : R - 1];
+  }
+  return o;
+}
+
+// Batched eval_counts_body: same sub-wave-per-path walk, same rounds, the
+// same select-not-add-zero handling of slots past hi. After the 16-lane
+// reduce every lane holds every replica's o, so the epilogue is spread over
+// the lanes: sublane j owns replicas j and j + 16 (is_correct, dlogit, the
+// coalesced dO_R store and the two count accumulators). The block fold goes
+// through LDS to per-block partials [gridDim.x, R, 2]; counts are integers
+// below 2^24, so their fold order is free.
+template <int NT, bool VEC>
+__global__ void __launch_bounds__(256)
+cbow_eval_counts_rep_kernel(const float* __restrict__ s_R,
+                            const int* __restrict__ genes,
+                            const int* __restrict__ offs,
+                            const float* __restrict__ labels,
+                            long long P, long long p_split, int R,
+                            float* __restrict__ partials,
+                            float* __restrict__ dO_R, float inv_b) {
+  constexpr int NR = NT * 4;
+  constexpr int NK = NR > SUBW ? 2 : 1;        // replicas owned per sublane
+  const int subs_per_block = blockDim.x / SUBW;
+  const int sublane = threadIdx.x & (SUBW - 1);
+  const int sub = threadIdx.x / SUBW;
+  const long long stride = (long long)gridDim.x * subs_per_block;
+  float c0[NK], c1[NK];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) { c0[k] = 0.f; c1[k] = 0.f; }
+  long long p = (long long)blockIdx.x * subs_per_block + sub;
+  int lo = 0, hi = 0;
+  float y = 0.f;
+  if (p < P) { lo = offs[p]; hi = offs[p + 1]; y = labels[p]; }
+  while (p < P) {
+    const long long pn = p + stride;
+    const long long pc = pn < P ? pn : P - 1;
+    const int lo_n = offs[pc], hi_n = offs[pc + 1];
+    const float y_n = labels[pc];
+    float part[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) part[r] = 0.f;
+    for (int i0 = lo + sublane; i0 - sublane < hi; i0 += EVAL_U * SUBW) {
+      int id[EVAL_U];
+#pragma unroll
+      for (int u = 0; u < EVAL_U; ++u) {
+        const int i = i0 + u * SUBW;
+        id[u] = __builtin_nontemporal_load(&genes[i < hi ? i : hi - 1]);
+      }
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        f32x4 sv[EVAL_U];
+#pragma unroll
+        for (int u = 0; u < EVAL_U; ++u)
+          sv[u] = rep_gather4<VEC>(s_R, id[u], R, t);
+#pragma unroll
+        for (int u = 0; u < EVAL_U; ++u)
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            part[4 * t + k] = (i0 + u * SUBW < hi)
+                                  ? part[4 * t + k] + sv[u][k]
+                                  : part[4 * t + k];
+      }
+    }
+    float o[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) o[k] = 0.f;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const float orr = subwave_sum16(part[r]);
+      if ((r & (SUBW - 1)) == sublane) o[r / SUBW] = orr;
+    }
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const int r = sublane + k * SUBW;
+      if (r < R) {
+        const float corr = is_correct(o[k], y);
+        if (p < p_split) c0[k] += corr; else c1[k] += corr;
+        if (dO_R && p < p_split) dO_R[p * R + r] = dlogit(o[k], y, inv_b);
+      }
+    }
+    p = pn; lo = lo_n; hi = hi_n; y = y_n;
+  }
+  // block fold: slot [2k + split][thread]; thread (k, split, j) sums the
+  // block's sub-waves for replica j + 16k
+  __shared__ float sm[4 * 256];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    sm[(2 * k) * 256 + threadIdx.x] = c0[k];
+    sm[(2 * k + 1) * 256 + threadIdx.x] = c1[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * NK * SUBW) {
+    const int which = threadIdx.x / SUBW;      // 2k + split
+    const int r = sublane + (which >> 1) * SUBW;
+    float tot = 0.f;
+    for (int sb = 0; sb < subs_per_block; ++sb)
+      tot += sm[which * 256 + sb * SUBW + sublane];
+    if (r < R)
+      partials[((long long)blockIdx.x * R + r) * 2 + (which & 1)] = tot;
+  }
+}
+
+// one block per replica folds its [n_blocks, 2] column of the partials
+extern "C" __global__ void __launch_bounds__(256)
+fold_partials_rep_kernel(const float* __restrict__ partials, int n_blocks,
+                         int R, float* __restrict__ counts_R) {
+  const int r = blockIdx.x;
+  float c0 = 0.f, c1 = 0.f;
+  for (int b = threadIdx.x; b < n_blocks; b += blockDim.x) {
+    c0 += partials[((long long)b * R + r) * 2];
+    c1 += partials[((long long)b * R + r) * 2 + 1];
+  }
+  block_fold2(c0, c1, counts_R + 2 * r);
+}
+
 // =============================================== fast path: c = X^T dO (det.)
 // One wave per gene segment (instances pre-sorted by gene, plan built once
 // per path set). Fixed tree-reduction order -> bitwise reproducible.
@@ -585,11 +729,71 @@ scatter_do_det_kernel(const int* __restrict__ inst_path,
   }
 }
 
+// Batched scatter_do_det_kernel: c_R [G, R] += X^T dO_R over the same plan.
+// Lane <-> instance as in the single kernel, so each inst_path entry is
+// loaded once for all replicas; per replica the four unroll accumulators,
+// their (p0 + p1) + (p2 + p3) join and the wave_sum tree are the single
+// kernel's. Lane r then adds replica r's total into c_R (one coalesced
+// R-float row per segment).
+template <int NT, bool VEC>
+__global__ void __launch_bounds__(256)
+scatter_do_rep_kernel(const int* __restrict__ inst_path,
+                      const int* __restrict__ seg_start,
+                      const int* __restrict__ seg_gene, int n_seg,
+                      const float* __restrict__ dO_R, int R,
+                      float* __restrict__ c_R) {
+  constexpr int NR = NT * 4;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  for (long long sidx = (long long)blockIdx.x * wpb + wib; sidx < n_seg;
+       sidx += (long long)gridDim.x * wpb) {
+    const int lo = seg_start[sidx], hi = seg_start[sidx + 1];
+    float acc[4][NR];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int r = 0; r < NR; ++r) acc[q][r] = 0.f;
+    int i = lo + lane;
+    for (; i + 3 * WAVE < hi; i += 4 * WAVE) {
+      int ip[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ip[q] = inst_path[i + q * WAVE];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        f32x4 d[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) d[q] = rep_gather4<VEC>(dO_R, ip[q], R, t);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[q][4 * t + k] += d[q][k];
+      }
+    }
+    for (; i < hi; i += WAVE) {
+      const int ip = inst_path[i];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const f32x4 d = rep_gather4<VEC>(dO_R, ip, R, t);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[0][4 * t + k] += d[k];
+      }
+    }
+    float mine = 0.f;                          // lane r keeps replica r's sum
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const float v = wave_sum((acc[0][r] + acc[1][r]) +
+                               (acc[2][r] + acc[3][r]));
+      if (lane == r) mine = v;
+    }
+    if (lane < R) c_R[(long long)seg_gene[sidx] * R + lane] += mine;
+  }
+}
+
 // ============================================================== K7: TF1 Adam
 // theta -= lr_t * m / (sqrt(v) + eps); lr_t precomputed on host.
 // rank-1 variant forms grad[g*h+j] = c[g] * who[j] on the fly (the linear
 // CBOW's dW_ih is rank-1, see models/cbow.py) — no G*h grad tensor exists.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 extern "C" __global__ void __launch_bounds__(256)
 adam_rank1_kernel(float* __restrict__ W, float* __restrict__ m,
@@ -926,6 +1130,7 @@ gemv_rows_kernel(const float* __restrict__ W, const float* __restrict__ x,
   }
 }
 
+
 // out[j] = sum_g c[g] * W[g, j] (the dW_ho = W_ih^T c reduction): each
 // block accumulates a row range into a private [h] partial; a second pass
 // folds the partials (atomic-free).
@@ -965,6 +1170,128 @@ fold_cols_kernel(const float* __restrict__ partials, int n_blocks, int h,
     a += partials[(long long)b * h + col];
   a = wave_sum(a);
   if (lane == 0) out[col] = a;
+}
+
+// ============================ replica-batched fused tail and GEMV (see REP_MAX)
+// blockIdx.y = replica r over the single launch's per-replica geometry;
+// W/m/v [R, G, h], who/mO/vO [R, h], c_R and s_R [G, R] (read / written at
+// stride R), gw_partials [R, gridDim.x, h]. The three kernels restate
+// adam_rank1_kernel (fused form), fold_gw_adam_kernel and gemv_rows_kernel
+// expression by expression, so the compiler contracts the same FMAs and
+// each replica's result is bitwise the single kernel's;
+// tests/test_gpu_replicates.py holds them to it. They deliberately share no
+// body with the single entry points: routed through a common body those
+// compiled to the same instructions in another order, so the single
+// kernels keep their text and, with it, their instruction streams
+// (docs/KERNELS.md).
+extern "C" __global__ void __launch_bounds__(256)
+adam_rank1_rep_kernel(float* __restrict__ W, float* __restrict__ m,
+                      float* __restrict__ v, const float* __restrict__ c_R,
+                      const float* __restrict__ who, long long G, int h,
+                      int R, const float* __restrict__ lr_t_ptr, float b1,
+                      float b2, float eps, float* __restrict__ gw_partials) {
+  const long long r = blockIdx.y;
+  const float lr_t = lr_t_ptr[0];
+  f32x4* W4 = (f32x4*)(W + r * G * h);
+  f32x4* m4 = (f32x4*)(m + r * G * h);
+  f32x4* v4 = (f32x4*)(v + r * G * h);
+  const f32x4* who4 = (const f32x4*)(who + r * h);
+  const float* c = c_R + r;
+  const int h4 = h / 4;
+  const int rpb = blockDim.x / h4;             // rows per block (h <= 1024)
+  const int lrow = (int)threadIdx.x / h4;      // this thread's row-in-block
+  const int j4 = (int)threadIdx.x - lrow * h4; // and column group
+  const f32x4 wj = who4[j4];
+  f32x4 gw_acc = {0.f, 0.f, 0.f, 0.f};
+  for (long long g = (long long)blockIdx.x * rpb + lrow; g < G;
+       g += (long long)gridDim.x * rpb) {
+    const long long i = g * h4 + j4;
+    const float cg = c[g * R];
+    f32x4 mm = __builtin_nontemporal_load(&m4[i]);
+    f32x4 vv = __builtin_nontemporal_load(&v4[i]);
+    f32x4 ww = __builtin_nontemporal_load(&W4[i]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      gw_acc[k] += cg * ww[k];                 // pre-update W row
+      const float grad = cg * wj[k];
+      mm[k] = b1 * mm[k] + (1.f - b1) * grad;
+      vv[k] = b2 * vv[k] + (1.f - b2) * grad * grad;
+      ww[k] -= lr_t * mm[k] / (sqrtf(vv[k]) + eps);
+    }
+    __builtin_nontemporal_store(mm, &m4[i]);
+    __builtin_nontemporal_store(vv, &v4[i]);
+    __builtin_nontemporal_store(ww, &W4[i]);
+  }
+  // per-block fold: slots [rpb][h] in LDS, summed ascending lrow
+  __shared__ float gw_slots[256 * 4];          // rpb * h = 1024 floats
+  float* slot = gw_slots + (lrow * h4 + j4) * 4;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) slot[k] = gw_acc[k];
+  __syncthreads();
+  if (lrow == 0) {
+    f32x4 tot = {0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < rpb; ++q) {
+      const float* sl = gw_slots + (q * h4 + j4) * 4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) tot[k] += sl[k];
+    }
+    float* out = gw_partials + (r * gridDim.x + blockIdx.x) * h + j4 * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = tot[k];
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+fold_gw_adam_rep_kernel(const float* __restrict__ partials, int n_blocks,
+                        int h, float* __restrict__ who,
+                        float* __restrict__ mO, float* __restrict__ vO,
+                        const float* __restrict__ lr_t_ptr, float b1,
+                        float b2, float eps) {
+  const long long r = blockIdx.y;
+  partials += r * n_blocks * h;
+  who += r * h; mO += r * h; vO += r * h;
+  const float lr_t = lr_t_ptr[0];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  for (int i = blockIdx.x * wpb + wib; i < h; i += gridDim.x * wpb) {
+    float g = 0.f;
+    for (int b = lane; b < n_blocks; b += WAVE)
+      g += partials[(long long)b * h + i];
+    g = wave_sum(g);
+    if (lane == 0) {
+      const float mm = b1 * mO[i] + (1.f - b1) * g;
+      const float vv = b2 * vO[i] + (1.f - b2) * g * g;
+      mO[i] = mm;
+      vO[i] = vv;
+      who[i] -= lr_t * mm / (sqrtf(vv) + eps);
+    }
+  }
+}
+
+template <int HPL>
+__global__ void __launch_bounds__(256)
+gemv_rows_rep_kernel(const float* __restrict__ W, const float* __restrict__ x,
+                     long long G, int h, int R, float* __restrict__ out) {
+  const long long r = blockIdx.y;
+  W += r * G * h;
+  x += r * h;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  const int col0 = lane * HPL;
+  float xv[HPL];
+  __builtin_memcpy(xv, x + col0, HPL * sizeof(float));
+  for (long long g = (long long)blockIdx.x * wpb + wib; g < G;
+       g += (long long)gridDim.x * wpb) {
+    float acc[HPL];
+    __builtin_memcpy(acc, W + g * (long long)h + col0, HPL * sizeof(float));
+    float p = 0.f;
+#pragma unroll
+    for (int k = 0; k < HPL; ++k) p += acc[k] * xv[k];
+    const float o = wave_sum(p);
+    if (lane == 0) out[g * R + r] = o;
+  }
 }
 
 // =============================================================== bf16 cast

@@ -173,6 +173,17 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
                           epochs_run=0, acc_val_history=[],
                           epoch_times_s=[], wall_to_acc_s=None)
         log("    (loaded weights from %s; training skipped)" % cfg.load_model)
+    elif cfg.replicates > 1:
+        if ctx.world != 1:
+            raise ValueError("replicates > 1 runs on one process; it "
+                             f"conflicts with world size {ctx.world}")
+        from .models.replicas import ReplicaTrainer
+        log("    replicates: %d" % cfg.replicates)
+        rep_t0 = time.perf_counter()
+        with timers.phase("train"):
+            rep_res = ReplicaTrainer(cfg, n_genes, device, log=log).train(
+                ps, cfg.replicates)
+        res = rep_res[0]        # replica 0 is the run without the flag
     else:
         trainer = CbowTrainer(cfg, n_genes, device, ctx, log=log)
         with timers.phase("train"):
@@ -233,6 +244,47 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
             biomarkers = select_biomarkers(W, lg, data["expr"], data["label"],
                                            data["gene"], cfg.num_biomarker,
                                            d_all=d_all, t_all=t_all)
+    stab = None
+    if cfg.replicates > 1:
+        # steps 5-6 once more per further replica, through the same calls
+        # and backends; the t-scores do not depend on the weights, so one
+        # vector serves every replica
+        from . import stability
+        from .scoring import t_scores as host_t_scores
+        with timers.phase("replicates_steps56"):
+            sc0 = scores if scores is not None else score_genes(
+                W, lg, data["expr"], data["label"], data["gene"],
+                cfg.num_biomarker, d_all=d_all, t_all=t_all, rank_only=True)
+            t_once = t_all if t_all is not None else host_t_scores(
+                data["expr"], np.asarray(data["label"]))
+            lg_all, sel_all, gs_all = [lg], [sc0["is_biomarker"]], \
+                [sc0["gene_score"]]
+            for rr in rep_res[1:]:
+                W_r = rr.W_ih.float().cpu().numpy()
+                W_r_dev = d_r = None
+                if W_dev is not None:
+                    W_r_dev = rr.W_ih.float().to(device).contiguous()
+                if cfg.scoring_backend == "device":
+                    from . import ops
+                    d_r = ops.row_norms(W_r_dev).cpu().numpy()
+                lg_r = find_lgroups(
+                    W_r_dev if cfg.kmeans_backend == "hip" else W_r,
+                    freq.cpu().numpy(), cfg.compat_lgroup_bug,
+                    backend=cfg.kmeans_backend, device=device, info={})
+                sc_r = score_genes(W_r, lg_r, data["expr"], data["label"],
+                                   data["gene"], cfg.num_biomarker,
+                                   d_all=d_r, t_all=t_once, rank_only=True)
+                lg_all.append(lg_r)
+                sel_all.append(sc_r["is_biomarker"])
+                gs_all.append(sc_r["gene_score"])
+            stab = stability.summarize(np.stack(lg_all), np.stack(sel_all),
+                                       np.stack(gs_all), cfg.num_biomarker)
+        jsonl.emit("replicates", R=cfg.replicates,
+                   stop_epochs=[r.stop_epoch for r in rep_res],
+                   acc_val=[r.acc_val for r in rep_res],
+                   acc_tr=[r.acc_tr for r in rep_res],
+                   jaccard=stab["jaccard"],
+                   seconds=time.perf_counter() - rep_t0)
     if cfg.permutations > 0:
         perm_seed = cfg.perm_seed if cfg.perm_seed is not None else (
             cfg.seed if cfg.seed is not None
@@ -277,7 +329,14 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
             f5 = gio.write_neighbors(cfg.result_name, data["gene"], nbr_q,
                                      nbr[0], nbr[1], lg, biomarkers)
             log("    %s" % f5)
+        if stab is not None:
+            log("    %s" % gio.write_stability(cfg.result_name, data["gene"],
+                                               stab))
+            log("    %s" % gio.write_consensus(cfg.result_name, data["gene"],
+                                               stab))
 
+    if stab is not None:
+        result["stability"] = stab
     result.update({"lgroups": lg, "biomarkers": biomarkers,
                    "timers": timers.summary()})
     jsonl.emit("done", **{k: v for k, v in result.items()

@@ -156,6 +156,39 @@ def synth_dataset(n_genes: int, n_edges: int, n_samples: int,
             "samples": names, "edge_idx": edge_idx, "module": module}
 
 
+def synth_pathset(n_genes: int, n_paths: int, n_modules: int = 16,
+                  len_path: int = 80, mean_len: float = 21.0, seed: int = 0,
+                  label_noise: float = 0.1):
+    """A path set of the shape step 3 produces, without walking a graph (the
+    trainer benchmarks need the shapes, not the biology): path p stays in
+    one module (a contiguous gene range under a seeded permutation, like a
+    walk inside one co-expression module), its genes are distinct, its
+    length is geometric with mean ~mean_len capped at len_path (the ex_*
+    sets average ~21 genes with a tail at len_path), and its label is the
+    module's class with a share label_noise flipped. Returns (genes i32
+    [nnz], offsets i32 [P + 1], labels f32 [P])."""
+    rng = np.random.default_rng(seed)
+    msize = n_genes // n_modules
+    if msize < 1:
+        raise ValueError("need at least one gene per module")
+    cap = min(int(len_path), msize)
+    lens = np.minimum(rng.geometric(1.0 / mean_len, size=n_paths), cap)
+    module = rng.integers(0, n_modules, size=n_paths)
+    start = rng.integers(0, msize, size=n_paths)
+    offs = np.zeros(n_paths + 1, dtype=np.int64)
+    offs[1:] = np.cumsum(lens)
+    if offs[-1] >= 2 ** 31:
+        raise ValueError("path set exceeds the int32 instance index space")
+    path_of = np.repeat(np.arange(n_paths), lens)
+    k = np.arange(offs[-1]) - offs[path_of]              # position in path
+    perm = rng.permutation(n_genes)
+    genes = perm[module[path_of] * msize + (start[path_of] + k) % msize]
+    labels = (module % 2).astype(np.float32)
+    flip = rng.random(n_paths) < label_noise
+    labels[flip] = 1.0 - labels[flip]
+    return (genes.astype(np.int32), offs.astype(np.int32), labels)
+
+
 # -------------------------------------------------- file emission (ex_* style)
 def write_expression_tsv(path: str, genes: Sequence[str], samples: Sequence[str],
                          expr_sg: np.ndarray) -> None:
