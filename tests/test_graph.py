@@ -46,18 +46,32 @@ def test_csr_matches_dense_reference():
              rng.integers(0, G, size=(E, 2)) if a != b]
     edges += [(0, 1), (2, 3)]
 
+    import step3_cases as sc
+    listed = np.zeros((G, G), dtype=bool)
+    listed[[e[0] for e in edges], [e[1] for e in edges]] = True
     for group in (0, 1):
         dense = _dense_adj_reference(expr, labels, group, edges, G)
-        g = build_group_graph(torch.from_numpy(expr), torch.from_numpy(labels),
-                              group, torch.tensor(edges, dtype=torch.int32),
-                              G, mode="edge")
-        rebuilt = np.zeros((G, G), dtype=np.float32)
-        rp = g.row_ptr.numpy()
-        for i in range(G):
-            for k in range(rp[i], rp[i + 1]):
-                rebuilt[i, g.col_idx[k]] = g.weights[k]
-        assert np.allclose(rebuilt, dense, atol=1e-5), f"group {group}"
-        assert (rebuilt > 0).sum() > 0  # planted edges survive in some group
+        # the fp64 reference and the derived threshold band of step3_cases
+        C, mean, std = sc.pcc64_matrix(expr[labels == group])
+        band = sc.band_of(15, mean, std)
+        absC = np.abs(C)
+        ref = dict(A=np.where(listed & (absC > 0.5), absC, 0.0), absC=absC,
+                   band=band, listed=listed,
+                   undecided=listed & (np.abs(absC - 0.5) <= band))
+        for mode in ("edge", "gemm"):        # gemm: the mirror on the CPU
+            g = build_group_graph(torch.from_numpy(expr),
+                                  torch.from_numpy(labels), group,
+                                  torch.tensor(edges, dtype=torch.int32),
+                                  G, mode=mode)
+            rebuilt = np.zeros((G, G), dtype=np.float32)
+            rp = g.row_ptr.numpy()
+            for i in range(G):
+                for k in range(rp[i], rp[i + 1]):
+                    rebuilt[i, g.col_idx[k]] = g.weights[k]
+            assert np.allclose(rebuilt, dense, atol=1e-5), (group, mode)
+            assert (rebuilt > 0).sum() > 0  # planted edges survive in some group
+            sc.compare_banded(sc.csr_to_dense(g, G), ref,
+                              what=f"group {group} {mode}")
 
 
 def test_duplicate_edges_dedup():
