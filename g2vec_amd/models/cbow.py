@@ -28,12 +28,24 @@ Reference-semantics notes:
     (keep-last-good semantics, G2Vec.py:276-283)
   - Adam is TF1 AdamOptimizer (dense moments; lr_t = lr*sqrt(1-b2^t)/(1-b1^t))
   - init: truncated normal, stddev 1/sqrt(hidden), +-2 sigma (G2Vec.py:234-235)
+
+Layout of the trainer: setup() returns a declared TrainState. Every runner
+advances the fast full-batch epoch through ONE step (_step_epoch) or ONE
+block replay (_replay_block), applies the dip rule through ONE StopTracker
+and converts counts through accuracies(). The runners differ only in where
+the last-good weights live: run_epochs_sync (W_keep; also the minibatch /
+general / checkpointing runner), run_epochs_pipelined (rolling snapshots;
+fixed-epoch runs take the deferred-readback _run_epochs_kblocked) and
+run_epochs_kgranular (restore-and-replay). train() picks one and hands its
+on_epoch callback to the one _Reporter that owns the transcript and the
+TrainResult.
 """
 from __future__ import annotations
 
 import dataclasses
+import operator
 import time
-from typing import List, Optional
+from typing import Any, List, Optional
 
 import torch
 
@@ -64,6 +76,137 @@ class TrainResult:
     acc_val_history: List[float]
     epoch_times_s: List[float]
     wall_to_acc_s: Optional[float]   # wall-clock until val-ACC >= 0.88 (None if never)
+
+
+@dataclasses.dataclass
+class TrainState:
+    """Everything setup() builds and the runners mutate. The lazily filled
+    fields (graphs and per-runner buffers) are declared here too, so that a
+    reader — and bench.py, which looks at graph / kgraph / pipe_bufs — sees
+    what a state can hold."""
+    W: torch.Tensor
+    who: torch.Tensor
+    mW: torch.Tensor
+    vW: torch.Tensor
+    mO: torch.Tensor
+    vO: torch.Tensor
+    W_keep: torch.Tensor             # keep-last-good snapshot (sync runner)
+    tr: PathSet
+    vl: PathSet
+    plan: Any                        # gene-sorted instance plan (backward)
+    inv_b: float
+    batches: list
+    W16: Optional[torch.Tensor] = None      # general path, bf16/fp16 copy
+    t_adam: int = 0
+    epoch_idx: int = 0
+    # persistent fast-path buffers (stable addresses across hipGraph replays)
+    s_buf: Optional[torch.Tensor] = None
+    lrt_buf: Optional[torch.Tensor] = None
+    counts_buf: Optional[torch.Tensor] = None
+    dO_buf: Optional[torch.Tensor] = None   # pending dlogits of the next step
+    ev_genes: Optional[torch.Tensor] = None  # concatenated train+val eval set
+    ev_offsets: Optional[torch.Tensor] = None
+    ev_labels: Optional[torch.Tensor] = None
+    graph: Any = None                # per-epoch hipGraph (_ensure_graph)
+    graph_failed: bool = False
+    kbufs: Optional[tuple] = None    # (klrt [K], kcounts [K, 2])
+    kgraph: Any = None               # K-epoch block graph (_ensure_kgraph)
+    kblock_k: Optional[int] = None   # K of the recorded block graph
+    kgraph_failed: bool = False
+    run_bufs: Optional[tuple] = None   # fixed-epoch runner: (pinned lr_t
+                                       # staging, device schedule, history)
+    pipe_bufs: Optional[tuple] = None  # pipelined runner: (pinned counts,
+                                       # rolling snapshots | None, events)
+
+
+# the tensors of the mutable epoch state: with t_adam and epoch_idx they are
+# what a snapshot/restore or a train-state checkpoint has to carry
+EPOCH_TENSORS = ("W", "who", "mW", "vW", "mO", "vO", "dO_buf")
+_epoch_tensors = operator.attrgetter(*EPOCH_TENSORS)
+
+
+def accuracies(counts, n_tr: int, n_vl: int) -> tuple:
+    """(acc_tr, acc_val) from one epoch's two correct-counts (a host array
+    or pinned tensor: callers read a whole history back at once, because
+    per-element float(tensor[i, j]) on a fresh readback costs ~2.4 us)."""
+    return float(counts[0]) / max(n_tr, 1), float(counts[1]) / max(n_vl, 1)
+
+
+def capture_graph(body, log, label: str):
+    """Record body() into a hipGraph (recording executes nothing). Returns
+    the graph, or None after logging `label` with the error — the caller
+    then sets its *_failed flag and stays on its eager path."""
+    try:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            body()
+        return g
+    except Exception as e:  # noqa: BLE001
+        log(label % repr(e))
+        return None
+
+
+class StopTracker:
+    """The reference dip rule with its bookkeeping (G2Vec.py:276-283): fed
+    (epoch, acc_tr, acc_val) in order, feed() is True at the first epoch
+    whose val-ACC is strictly below the previous one's. `hist` includes the
+    dip epoch; before_val / before_tr stay the last good epoch's and
+    stop_epoch is the epoch BEFORE the dip. Which weights are that epoch's
+    is the runner's business."""
+
+    def __init__(self, early_stop: bool, before_val: float = -1.0,
+                 before_tr: float = -1.0, hist: Optional[list] = None):
+        self.early_stop = early_stop
+        self.before_val, self.before_tr = before_val, before_tr
+        self.hist: List[float] = hist if hist is not None else []
+        self.stop_epoch = -1
+
+    def feed(self, epoch: int, acc_tr: float, acc_val: float) -> bool:
+        self.hist.append(acc_val)
+        if self.early_stop and acc_val < self.before_val:
+            self.stop_epoch = epoch - 1
+            return True
+        self.before_val, self.before_tr = acc_val, acc_tr
+        return False
+
+
+class _Reporter:
+    """The training transcript, the timings and the TrainResult: on_epoch
+    is the runners' per-epoch callback, finish() closes the run."""
+
+    def __init__(self, log, before_val: float = -1.0, before_tr: float = -1.0):
+        self.log = log
+        self.epoch_times: List[float] = []
+        self.wall_to_acc = None
+        self.prev = self.cur = (before_val, before_tr)
+        self.log("     Start training the modified CBOW with early stopping")
+        self.t0 = self.last = self.blk_t0 = time.perf_counter()
+
+    def on_epoch(self, e: int, acc_tr: float, acc_val: float) -> None:
+        now = time.perf_counter()
+        self.epoch_times.append(now - self.last)
+        self.last = now
+        self.prev, self.cur = self.cur, (acc_val, acc_tr)
+        if self.wall_to_acc is None and acc_val >= CbowTrainer.ACC_TARGET:
+            self.wall_to_acc = now - self.t0
+        if e % 5 == 0:
+            self.log("    - Epoch: %03d\tACC[val]=%.4f\tACC[tr]=%.4f (%.3f sec)"
+                     % (e, acc_val, acc_tr, now - self.blk_t0))
+            self.blk_t0 = now
+
+    def finish(self, W_ih, hist, stop_epoch: int) -> TrainResult:
+        acc_val, acc_tr = self.cur
+        if stop_epoch >= 0:          # the last callback was the dip epoch
+            acc_val, acc_tr = self.prev
+            self.log("    - Epoch(stop): %03d\tACC[val]=%.4f\tACC[tr]=%.4f (%.3f sec)"
+                     % (stop_epoch, acc_val, acc_tr,
+                        time.perf_counter() - self.blk_t0))
+        self.log("    Optimization Finish")
+        return TrainResult(W_ih=W_ih, stop_epoch=stop_epoch,
+                           acc_val=acc_val, acc_tr=acc_tr,
+                           epochs_run=len(hist), acc_val_history=hist,
+                           epoch_times_s=self.epoch_times,
+                           wall_to_acc_s=self.wall_to_acc)
 
 
 class CbowTrainer:
@@ -183,10 +326,9 @@ class CbowTrainer:
         self.ctx.broadcast_(order)
         return order
 
-    # ------------------------------------------------------------------ setup
-    def setup(self, ps: PathSet, pre_sharded: bool = False):
+    def setup(self, ps: PathSet, pre_sharded: bool = False) -> TrainState:
         """Initialise weights/optimizer state and split the path set.
-        Returns the mutable training state used by run_epoch()."""
+        Returns the mutable training state used by the runners."""
         cfg = self.cfg
         gen = None
         if cfg.seed is not None:
@@ -219,31 +361,28 @@ class CbowTrainer:
             # cache-resident slices instead of the whole table
             tr = self._locality_sort(tr)
             vl = self._locality_sort(vl)
-        st = type("TrainState", (), {})()
-        st.W, st.who = W, who
-        st.mW, st.vW = torch.zeros_like(W), torch.zeros_like(W)
-        st.mO, st.vO = torch.zeros_like(who), torch.zeros_like(who)
-        st.W_keep = W.clone()
-        st.tr, st.vl = tr, vl
-        st.W16 = None
-        if use_general and cfg.dtype != "fp32":
-            st.W16 = (W.bfloat16() if cfg.dtype == "bf16" else W.half())
         # gene-sorted instance plan: drives the deterministic backward on
         # both trainer paths (genes never change across epochs). The
         # general path's row backward writes one dW row per segment, so it
         # takes the single-pass layout at every path count.
-        st.plan = ops.build_scatter_plan(tr.genes, tr.offsets, self.G,
-                                         slabs=not use_general)
+        plan = ops.build_scatter_plan(tr.genes, tr.offsets, self.G,
+                                      slabs=not use_general)
         if self.n_tr_global + self.n_vl_global == 0:
             raise ValueError(
                 "no paths to train on: the integrated path set is empty "
                 "(every walk was dropped as a cross-group duplicate, or "
                 "the PCC-thresholded graphs have no edges — check the "
                 "expression signal / --pcc-threshold)")
-        st.inv_b = 1.0 / max(self.n_tr_global, 1)
         P_loc = tr.n_paths
         bs = cfg.batch_size if cfg.batch_size > 0 else max(P_loc, 1)
-        st.batches = [(i, min(i + bs, P_loc)) for i in range(0, P_loc, bs)]
+        st = TrainState(
+            W=W, who=who, mW=torch.zeros_like(W), vW=torch.zeros_like(W),
+            mO=torch.zeros_like(who), vO=torch.zeros_like(who),
+            W_keep=W.clone(), tr=tr, vl=vl, plan=plan,
+            inv_b=1.0 / max(self.n_tr_global, 1),
+            batches=[(i, min(i + bs, P_loc)) for i in range(0, P_loc, bs)])
+        if use_general and cfg.dtype != "fp32":
+            st.W16 = (W.bfloat16() if cfg.dtype == "bf16" else W.half())
         if self.ctx.world > 1 and cfg.batch_size > 0:
             # lockstep minibatching: strided shards can differ by one
             # path, so per-rank batch COUNTS can differ — pad with empty
@@ -255,18 +394,13 @@ class CbowTrainer:
             self.ctx.allreduce_max_(nb)
             while len(st.batches) < int(nb.item()):
                 st.batches.append((P_loc, P_loc))
-        st.t_adam = 0
-        st.epoch_idx = 0
         # persistent fast-path buffers (stable addresses across hipGraph replays)
-        st.s_buf = None
         if not use_general:
             st.s_buf = torch.empty(self.G, dtype=torch.float32,
                                    device=self.device)
             ops.gemv_rows(W, who, st.s_buf)
         st.lrt_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
         st.counts_buf = torch.zeros(2, dtype=torch.float32, device=self.device)
-        st.graph = None
-        st.graph_failed = False
         # concatenated train+val evaluation set: both accuracy splits ride
         # ONE forward kernel per epoch
         if not use_general and tr.n_paths + vl.n_paths > 0:
@@ -274,20 +408,10 @@ class CbowTrainer:
             st.ev_genes = torch.cat([tr.genes, vl.genes]).contiguous()
             st.ev_offsets = torch.cat([tr.offsets, off_vl[1:]]).contiguous()
             st.ev_labels = torch.cat([tr.labels, vl.labels]).contiguous()
-            # NOTE: an instance-parallel segmented-scan eval
-            # (eval_scan_kernel) was built and A/B-measured against the
-            # subwave-per-path kernel — slower at every tested shape
-            # (44 vs 21.5 us at the ex_* path-length distribution, tie at
-            # 1M genes; tools/bench_eval.py, profiles/README.md). The
-            # subwave kernel stays the epoch-body eval; the scan pair
-            # remains available + tested as the research alternative.
-        else:
-            st.ev_genes = None
         # full-batch steady state fuses the forward into the PREVIOUS
         # epoch's eval (same s, same train paths — the gather runs once per
         # weight version): dO_buf carries the pending dlogits; seed it here
         # from the initial weights (the one standalone forward of a run)
-        st.dO_buf = None
         if not use_general and cfg.batch_size == 0:
             st.dO_buf = torch.zeros(tr.n_paths, dtype=torch.float32,
                                     device=self.device)
@@ -363,22 +487,8 @@ class CbowTrainer:
         cfg = self.cfg
         fast_full = cfg.trainer_path != "general" and cfg.batch_size == 0
         if fast_full:
-            st.t_adam += 1
-            on_gpu = self.device.type == "cuda"
-            if on_gpu:
-                st.lrt_buf.fill_(ops.tf1_lr_t(cfg.lr, self.B1, self.B2,
-                                              st.t_adam))
-            if on_gpu:
-                self._ensure_graph(st)
-            if st.graph is not None:
-                st.graph.replay()
-            else:
-                self._epoch_body_fast(st)
-            cc = st.counts_buf.cpu().numpy()
-            acc_tr = float(cc[0]) / max(self.n_tr_global, 1)
-            acc_val = float(cc[1]) / max(self.n_vl_global, 1)
-            st.epoch_idx += 1
-            return acc_tr, acc_val
+            self._step_epoch(st)
+            return self._accs(st.counts_buf.cpu().numpy())
 
         for (lo, hi) in st.batches:
             # empty pad batch (lockstep minibatching): zero local grad,
@@ -404,11 +514,34 @@ class CbowTrainer:
                     st.s_buf, split.genes, split.offsets, split.labels, 1.0, False)
                 counts[k] = corr.sum()
             self.ctx.allreduce_(counts)         # C3: one fused metric reduce
-            cc = counts.cpu().numpy()
-            acc_tr = float(cc[0]) / max(self.n_tr_global, 1)
-            acc_val = float(cc[1]) / max(self.n_vl_global, 1)
+            acc_tr, acc_val = self._accs(counts.cpu().numpy())
         st.epoch_idx += 1
         return acc_tr, acc_val
+
+    def _accs(self, counts) -> tuple:
+        return accuracies(counts, self.n_tr_global, self.n_vl_global)
+
+    def _step_epoch(self, st, **body_kw) -> None:
+        """Advance ONE fast full-batch epoch, asynchronously: bump t_adam,
+        stage lr_t, run the body, bump epoch_idx. body_kw are the optional
+        counts_out / lrt_slot / reduce_counts of _epoch_body_fast. lr_t
+        goes into st.lrt_buf with one fill launch unless the caller brings
+        a slot that already holds it (a slice of a staged schedule: no
+        launch). The per-epoch graph is a recording of the DEFAULT body,
+        so it is captured and replayed only when nothing is overridden;
+        an overridden body runs eagerly (at world>1 the recorded body's
+        metric all-reduce must not slip into a deferred-metric run)."""
+        st.t_adam += 1
+        if "lrt_slot" not in body_kw and self.device.type == "cuda":
+            st.lrt_buf.fill_(ops.tf1_lr_t(self.cfg.lr, self.B1, self.B2,
+                                          st.t_adam))
+        if not body_kw:
+            self._ensure_graph(st)
+        if not body_kw and st.graph is not None:
+            st.graph.replay()
+        else:
+            self._epoch_body_fast(st, **body_kw)
+        st.epoch_idx += 1
 
     def _ensure_graph(self, st) -> None:
         """Capture the epoch body into a hipGraph when eligible. At
@@ -424,37 +557,23 @@ class CbowTrainer:
                 self.cfg.use_hipgraph and st.graph is None and
                 not st.graph_failed and st.epoch_idx >= 1 and
                 self.ctx.graph_capture_ok()):
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._epoch_body_fast(st)
-                st.graph = g            # capture records without executing
-            except Exception as e:  # noqa: BLE001
-                st.graph_failed = True
-                self.log(f"    (hipGraph capture unavailable: {e!r}; "
-                         f"running eager)")
+            st.graph = capture_graph(
+                lambda: self._epoch_body_fast(st), self.log,
+                "    (hipGraph capture unavailable: %s; running eager)")
+            st.graph_failed = st.graph is None
 
     def _launch_epoch(self, st, slot: int, pinned, snaps, events,
                       keep: bool = True) -> None:
-        """Queue one whole epoch asynchronously: body (graph replay or
-        eager), D2H copy of the accuracy counts into pinned memory, rolling
-        weight snapshot, completion event. Stream order guarantees the copy
-        reads THIS epoch's counts before the next epoch's body overwrites
-        them."""
-        st.t_adam += 1
-        st.lrt_buf.fill_(ops.tf1_lr_t(self.cfg.lr, self.B1, self.B2,
-                                      st.t_adam))
-        self._ensure_graph(st)
-        if st.graph is not None:
-            st.graph.replay()
-        else:
-            self._epoch_body_fast(st)
+        """Queue one whole epoch asynchronously: the step, D2H copy of the
+        accuracy counts into pinned memory, rolling weight snapshot,
+        completion event. Stream order guarantees the copy reads THIS
+        epoch's counts before the next epoch's body overwrites them."""
+        self._step_epoch(st)
         pinned[slot].copy_(st.counts_buf, non_blocking=True)
         if keep:                            # rolling keep-last-good snapshot;
             snaps[slot][0].copy_(st.W)      # skipped when early_stop is off
             snaps[slot][1].copy_(st.who)    # (2 GB/epoch at the 1M x 512 cfg)
         events[slot].record()
-        st.epoch_idx += 1
 
     KBLOCK = 8   # epochs recorded per block graph (fixed-epoch runs)
 
@@ -493,38 +612,36 @@ class CbowTrainer:
             return
         if not self.ctx.graph_capture_ok():
             return
-        K = max(int(k), 1) if k is not None else getattr(
-            st, "kblock_k", self.KBLOCK)
-        if getattr(st, "kbufs", None) is None or st.kbufs[0].numel() != K:
+        K = max(int(k), 1) if k is not None else (st.kblock_k or self.KBLOCK)
+        if st.kbufs is None or st.kbufs[0].numel() != K:
             st.kbufs = (
                 torch.empty(K, dtype=torch.float32, device=self.device),
                 torch.zeros(K, 2, dtype=torch.float32, device=self.device))
             st.kgraph = None
-        if st.kgraph is None and not getattr(st, "kgraph_failed", False):
-            klrt, kcounts = st.kbufs[0], st.kbufs[1]
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    for j in range(K):
-                        self._epoch_body_fast(st, counts_out=kcounts[j],
-                                              lrt_slot=klrt[j:j + 1],
-                                              reduce_counts=False)
-                st.kgraph = g        # capture records without executing
+        if st.kgraph is None and not st.kgraph_failed:
+            klrt, kcounts = st.kbufs
+
+            def bodies():
+                for j in range(K):
+                    self._epoch_body_fast(st, counts_out=kcounts[j],
+                                          lrt_slot=klrt[j:j + 1],
+                                          reduce_counts=False)
+            # capture mutates no epoch state; on failure callers fall back
+            # to the per-epoch path / eager tail loop
+            st.kgraph = capture_graph(
+                bodies, self.log, "    (k-epoch block graph unavailable: "
+                                  "%s; running per-epoch)")
+            if st.kgraph is not None:
                 st.kblock_k = K
-            except Exception as e:  # noqa: BLE001
-                # capture mutates no epoch state; callers fall back to
-                # the per-epoch path / eager tail loop
+            else:
                 st.kgraph_failed = True
-                self.log(f"    (k-epoch block graph unavailable: {e!r}; "
-                         f"running per-epoch)")
 
     def kblock_eligible(self, st, n_epochs: int, early_stop: bool) -> bool:
         """Fixed-epoch runs go through the deferred-readback runner: block
         graphs where capture is available, eager epoch bodies otherwise
         (--no-hipgraph / failed probe / CPU) — either way zero mid-run D2H
         and ONE metric all-reduce for the whole run."""
-        return (not early_stop and
-                not getattr(st, "kgraph_failed", False) and
+        return (not early_stop and not st.kgraph_failed and
                 st.ev_genes is not None and n_epochs >= 2)
 
     def _run_epochs_kblocked(self, st, n_epochs: int, on_epoch):
@@ -546,128 +663,99 @@ class CbowTrainer:
         changes nothing observable. Runs on CPU too (eager bodies, same
         deferred schedule) so the gloo DP tier covers this exact path.
         Returns the run_epochs_pipelined tuple."""
-        K = self.KBLOCK
         on_gpu = self.device.type == "cuda"
         if st.epoch_idx == 0:    # one eager epoch: warm allocator/state
             warm = [self.run_epoch(st)]
         else:
             warm = []
         self._ensure_kgraph(st)
-        kgraph = getattr(st, "kgraph", None)
-        if kgraph is not None:
-            K = st.kblock_k          # recorded block size (pick_kblock)
         n_rest = n_epochs - len(warm)
-        n_blocks = (n_rest // K) if kgraph is not None else 0
-        n_tail = n_rest - n_blocks * K
-        if kgraph is not None:
-            klrt, kcounts = st.kbufs[0], st.kbufs[1]
+        # recorded block size (pick_kblock); epochs past the last whole
+        # block, or all of them without a graph, run as the eager tail
+        K = st.kblock_k if st.kgraph is not None else None
+        n_blocked = (n_rest // K) * K if K else 0
         # whole lr_t schedule staged to device ONCE; each block slices it
-        # with a stream-ordered D2D copy (a host-side refill of klrt could
-        # race a replay still queued behind it). The staging itself goes
-        # through a cached pinned buffer with a non-blocking H2D: a plain
-        # torch.tensor(..., device="cuda") synchronizes, and at ex scale
-        # that ~50 us is a measurable share of a 30 x 0.063 ms timed run.
+        # (_replay_block). The staging itself goes through a cached pinned
+        # buffer with a non-blocking H2D: a plain torch.tensor(...,
+        # device="cuda") synchronizes, and at ex scale that ~50 us is a
+        # measurable share of a 30 x 0.063 ms timed run.
         sched_vals = torch.tensor(
             [ops.tf1_lr_t(self.cfg.lr, self.B1, self.B2, st.t_adam + i)
              for i in range(1, n_rest + 1)], dtype=torch.float32)
         if on_gpu:
             cap = max(n_rest, 1)
-            bufs = getattr(st, "run_bufs", None)
-            if bufs is None or bufs[0].numel() < cap:
+            if st.run_bufs is None or st.run_bufs[0].numel() < cap:
                 st.run_bufs = (
                     torch.empty(cap, dtype=torch.float32, pin_memory=True),
                     torch.empty(cap, dtype=torch.float32,
                                 device=self.device),
                     torch.zeros(cap, 2, dtype=torch.float32,
                                 device=self.device))
-                bufs = st.run_bufs
-            pin, sched, hist_dev = bufs
+            pin, sched, hist_dev = st.run_bufs
             pin[:n_rest].copy_(sched_vals)               # host-side copy
-            sched = sched[:max(n_rest, 1)]
-            sched.copy_(pin[:sched.numel()], non_blocking=True)
-            hist_dev = hist_dev[:max(n_rest, 1)]
+            sched = sched[:cap]
+            sched.copy_(pin[:cap], non_blocking=True)
+            hist_dev = hist_dev[:cap]
         else:
             sched = sched_vals
             hist_dev = torch.zeros(max(n_rest, 1), 2, dtype=torch.float32,
                                    device=self.device)
-        for b in range(n_blocks):
-            klrt.copy_(sched[b * K:(b + 1) * K], non_blocking=True)
-            st.t_adam += K
-            st.epoch_idx += K
-            kgraph.replay()
-            hist_dev[b * K:(b + 1) * K].copy_(kcounts, non_blocking=True)
-        for j in range(n_tail):                # tail: eager bodies, same
-            e = n_blocks * K + j               # zero-readback scheme
-            st.t_adam += 1
-            st.epoch_idx += 1
-            self._epoch_body_fast(st, counts_out=st.counts_buf,
-                                  lrt_slot=sched[e:e + 1],
-                                  reduce_counts=False)
+        for lo in range(0, n_blocked, K or 1):
+            self._replay_block(st, sched[lo:lo + K], hist_dev[lo:lo + K])
+        for e in range(n_blocked, n_rest):     # tail: eager bodies, same
+            # zero-readback scheme; lr_t straight from its schedule slot
+            self._step_epoch(st, lrt_slot=sched[e:e + 1], reduce_counts=False)
             hist_dev[e].copy_(st.counts_buf, non_blocking=True)
-            if on_gpu and (j + 1) % 64 == 0:   # bound launch-queue depth on
-                torch.cuda.synchronize()       # long eager (world>1) runs
+            if on_gpu and (e - n_blocked + 1) % 64 == 0:   # bound launch-
+                torch.cuda.synchronize()   # queue depth, long eager runs
 
         if n_rest > 0:
             self.ctx.allreduce_(hist_dev)      # C3: ONE reduce for the run
         # the ONE host readback; .numpy() view because per-element
         # float(tensor[i, j]) costs ~2.4 us each — 60 of them were
         # ~145 us of a ~1.9 ms 30-epoch run (numpy indexing: ~11 us)
-        cc = hist_dev.cpu().numpy()
-        acc_tr = warm[-1][0] if warm else 0.0
-        hist = [h[1] for h in warm]
-        if on_epoch is not None and hist:
-            on_epoch(0, acc_tr, hist[0])
-        for e in range(n_rest):
-            acc_tr = float(cc[e, 0]) / max(self.n_tr_global, 1)
-            acc_val = float(cc[e, 1]) / max(self.n_vl_global, 1)
-            if on_epoch is not None:
-                on_epoch(len(hist), acc_tr, acc_val)
-            hist.append(acc_val)
-        return hist, -1, st.W, st.who, acc_tr
+        accs = warm + [self._accs(c) for c in hist_dev.cpu().numpy()[:n_rest]]
+        if on_epoch is not None:
+            for e, (acc_tr, acc_val) in enumerate(accs):
+                on_epoch(e, acc_tr, acc_val)
+        return ([a[1] for a in accs], -1, st.W, st.who,
+                accs[-1][0] if accs else 0.0)
+
+    def _replay_block(self, st, sched_slice, hist_out) -> None:
+        """Replay the recorded K-epoch block once: K lr_t values from
+        sched_slice into the graph's slots, then the K per-epoch counts
+        (local, not yet reduced) into hist_out. All stream-ordered D2D
+        copies — a host-side refill of klrt could race a replay still
+        queued behind it."""
+        klrt, kcounts = st.kbufs
+        klrt.copy_(sched_slice, non_blocking=True)
+        st.t_adam += st.kblock_k
+        st.epoch_idx += st.kblock_k
+        st.kgraph.replay()
+        hist_out.copy_(kcounts, non_blocking=True)
 
     def _snapshot(self, st):
         """Deep copy of the mutable epoch state (for k-granular replay)."""
-        return ([st.W.clone(), st.who.clone(), st.mW.clone(), st.vW.clone(),
-                 st.mO.clone(), st.vO.clone(),
-                 st.dO_buf.clone() if st.dO_buf is not None else None],
-                st.t_adam, st.epoch_idx)
+        return ([t.clone() if t is not None else None
+                 for t in _epoch_tensors(st)], st.t_adam, st.epoch_idx)
 
     def _restore(self, st, snap) -> None:
-        (ts, t_adam, epoch_idx) = snap
-        st.W.copy_(ts[0]); st.who.copy_(ts[1])
-        st.mW.copy_(ts[2]); st.vW.copy_(ts[3])
-        st.mO.copy_(ts[4]); st.vO.copy_(ts[5])
-        if ts[6] is not None:
-            st.dO_buf.copy_(ts[6])
-        st.t_adam = t_adam
-        st.epoch_idx = epoch_idx
+        saved, st.t_adam, st.epoch_idx = snap
+        for dst, src in zip(_epoch_tensors(st), saved):
+            if src is not None:
+                dst.copy_(src)
 
     def _run_block(self, st, k: int, hist_out) -> None:
         """k epoch bodies, per-epoch counts into hist_out[:k] (local, not
-        yet reduced). Uses the recorded KBLOCK graph when k matches."""
-        kgraph = getattr(st, "kgraph", None)
-        if kgraph is not None and k == getattr(st, "kblock_k", self.KBLOCK):
-            klrt, kcounts = st.kbufs[0], st.kbufs[1]
+        yet reduced). Uses the recorded block graph when k matches."""
+        if st.kgraph is not None and k == st.kblock_k:
             sched = torch.tensor(
                 [ops.tf1_lr_t(self.cfg.lr, self.B1, self.B2, st.t_adam + i)
                  for i in range(1, k + 1)],
                 dtype=torch.float32, device=self.device)
-            klrt.copy_(sched, non_blocking=True)
-            st.t_adam += k
-            st.epoch_idx += k
-            kgraph.replay()
-            hist_out[:k].copy_(kcounts, non_blocking=True)
-            return
+            return self._replay_block(st, sched, hist_out[:k])
         for j in range(k):
-            st.t_adam += 1
-            st.epoch_idx += 1
-            lrt = None
-            if self.device.type == "cuda":
-                st.lrt_buf.fill_(ops.tf1_lr_t(self.cfg.lr, self.B1, self.B2,
-                                              st.t_adam))
-                lrt = st.lrt_buf
-            self._epoch_body_fast(st, counts_out=st.counts_buf,
-                                  lrt_slot=lrt, reduce_counts=False)
+            self._step_epoch(st, reduce_counts=False)
             hist_out[j].copy_(st.counts_buf, non_blocking=True)
 
     def run_epochs_kgranular(self, st, n_epochs: int, k: int, on_epoch=None):
@@ -685,50 +773,41 @@ class CbowTrainer:
         small-problem multi-GPU epochs. Returns the run_epochs_pipelined
         tuple."""
         assert k >= 1
+        trk = StopTracker(True)
         if st.epoch_idx == 0:      # eager warm epoch (allocator/graph prep)
             a_tr0, a_val0 = self.run_epoch(st)
-            hist = [a_val0]
             if on_epoch is not None:
                 on_epoch(0, a_tr0, a_val0)
+            trk.feed(0, a_tr0, a_val0)
             if n_epochs == 1:
-                return hist, -1, st.W, st.who, a_tr0
-        else:
-            hist = []
+                return trk.hist, -1, st.W, st.who, a_tr0
         self._ensure_kgraph(st)
         hist_dev = torch.zeros(k, 2, dtype=torch.float32, device=self.device)
-        before_val = hist[-1] if hist else -1.0
         acc_tr = 0.0
-        e = len(hist)
+        e = len(trk.hist)
         while e < n_epochs:
             blk = min(k, n_epochs - e)
             snap = self._snapshot(st)
             self._run_block(st, blk, hist_dev)
             self.ctx.allreduce_(hist_dev[:blk])     # one reduce per block
             cc = hist_dev[:blk].cpu().numpy()       # one D2H per block
-            stop_at = -1
             for j in range(blk):
-                a_tr = float(cc[j, 0]) / max(self.n_tr_global, 1)
-                a_val = float(cc[j, 1]) / max(self.n_vl_global, 1)
-                hist.append(a_val)                  # dip epoch included,
-                if on_epoch is not None:            # like the sync loop
+                a_tr, a_val = self._accs(cc[j])
+                if on_epoch is not None:
                     on_epoch(e + j, a_tr, a_val)
-                if a_val < before_val:
-                    stop_at = e + j                 # dip epoch
-                    break
+                if trk.feed(e + j, a_tr, a_val):
+                    # dip at e + j: rewind to the state after stop_epoch —
+                    # restore the block start (post-(e-1)) and
+                    # deterministically re-run up to it; the body has no
+                    # RNG, so the replayed weights are bitwise the
+                    # epoch-granular ones
+                    self._restore(st, snap)
+                    if j > 0:
+                        self._run_block(st, j, hist_dev)
+                    return trk.hist, trk.stop_epoch, st.W, st.who, acc_tr
                 acc_tr = a_tr
-                before_val = a_val
-            if stop_at >= 0:
-                # rewind to post-(stop_at - 1) state: restore the block
-                # start (post-(e-1)) and deterministically re-run
-                # (stop_at - e) epochs — the body has no RNG, so the
-                # replayed weights are bitwise the epoch-granular ones
-                self._restore(st, snap)
-                n_replay = stop_at - e
-                if n_replay > 0:
-                    self._run_block(st, n_replay, hist_dev)
-                return hist, stop_at - 1, st.W, st.who, acc_tr
             e += blk
-        return hist, -1, st.W, st.who, acc_tr
+        return trk.hist, -1, st.W, st.who, acc_tr
 
     def run_epochs_pipelined(self, st, n_epochs: int, early_stop: bool,
                              on_epoch=None):
@@ -745,7 +824,7 @@ class CbowTrainer:
         on_gpu = self.device.type == "cuda"
         if self.kblock_eligible(st, n_epochs, early_stop):
             return self._run_epochs_kblocked(st, n_epochs, on_epoch)
-        if getattr(st, "pipe_bufs", None) is None:
+        if st.pipe_bufs is None:
             st.pipe_bufs = (
                 [torch.empty(2, dtype=torch.float32, pin_memory=on_gpu)
                  for _ in range(DEPTH)],
@@ -758,11 +837,7 @@ class CbowTrainer:
             snaps = [(torch.empty_like(st.W), torch.empty_like(st.who))
                      for _ in range(DEPTH)]
             st.pipe_bufs = (pinned, snaps, events)
-        hist = []
-        before_val = -1.0
-        stop_epoch = -1
-        launched = 0
-        acc_tr = 0.0
+        trk = StopTracker(early_stop)
         self._launch_epoch(st, 0, pinned, snaps, events, keep=early_stop)
         launched = 1
         e = 0
@@ -772,72 +847,100 @@ class CbowTrainer:
                                    events, keep=early_stop)
                 launched += 1
             events[e % DEPTH].synchronize()
-            cc = pinned[e % DEPTH]
-            acc_tr = float(cc[0]) / max(self.n_tr_global, 1)
-            acc_val = float(cc[1]) / max(self.n_vl_global, 1)
-            hist.append(acc_val)
+            acc_tr, acc_val = self._accs(pinned[e % DEPTH])
             if on_epoch is not None:
                 on_epoch(e, acc_tr, acc_val)
-            if early_stop and acc_val < before_val:
-                stop_epoch = e - 1      # dip at e: report/return epoch e-1
-                return (hist, stop_epoch, snaps[(e - 1) % DEPTH][0],
-                        snaps[(e - 1) % DEPTH][1], acc_tr)
-            before_val = acc_val
+            if trk.feed(e, acc_tr, acc_val):
+                # dip at e: report/return epoch e-1 from its rolling slot
+                W_good, who_good = snaps[trk.stop_epoch % DEPTH]
+                return trk.hist, trk.stop_epoch, W_good, who_good, acc_tr
             e += 1
             if e >= n_epochs:
-                return hist, -1, st.W, st.who, acc_tr
+                return trk.hist, -1, st.W, st.who, acc_tr
 
-    # ------------------------------------------------------------------ train
+    def run_epochs_sync(self, st, n_epochs: int, early_stop: bool,
+                        on_epoch=None, tracker: Optional[StopTracker] = None,
+                        after_epoch=None):
+        """The synchronous runner: one run_epoch and one readback per
+        epoch, on any device and trainer path (minibatch and general
+        included), keep-last-good in st.W_keep (G2Vec.py:283). Epochs are
+        aligned with the host, so this is the runner under train-state
+        checkpointing: it starts at st.epoch_idx (non-zero after
+        load_train_state), takes a tracker primed with the resumed
+        before_val / before_tr / history, and calls after_epoch(epoch,
+        tracker) once per kept epoch. Returns the run_epochs_pipelined
+        tuple."""
+        trk = tracker if tracker is not None else StopTracker(early_stop)
+        acc_tr = trk.before_tr
+        for epoch in range(st.epoch_idx, n_epochs):
+            acc_tr, acc_val = self.run_epoch(st)
+            if on_epoch is not None:
+                on_epoch(epoch, acc_tr, acc_val)
+            if trk.feed(epoch, acc_tr, acc_val):
+                break
+            st.W_keep.copy_(st.W)
+            if after_epoch is not None:
+                after_epoch(epoch, trk)
+        return trk.hist, trk.stop_epoch, st.W_keep, st.who, acc_tr
+
     # --------------------------------------------------- train-state ckpt
+    def _fingerprint(self) -> dict:
+        return {"n_genes": self.G, "hidden": self.h, "seed": self.cfg.seed,
+                "lr": self.cfg.lr, "trainer_path": self.cfg.trainer_path,
+                "world": self.ctx.world, "rank": self.ctx.rank}
+
     def save_train_state(self, st, path: str, extra: dict) -> None:
         """Epoch-boundary training checkpoint: weights,
         TF1-Adam moments, the fused-eval dlogit carry, early-stop
         trackers, and a config fingerprint. Resuming from it continues
         the EXACT trajectory (epoch bodies are deterministic)."""
-        blob = {
-            "W": st.W.cpu(), "who": st.who.cpu(),
-            "mW": st.mW.cpu(), "vW": st.vW.cpu(),
-            "mO": st.mO.cpu(), "vO": st.vO.cpu(),
-            "W_keep": st.W_keep.cpu(),
-            "dO_buf": (st.dO_buf.cpu() if st.dO_buf is not None else None),
-            "t_adam": st.t_adam, "epoch_idx": st.epoch_idx,
-            "fingerprint": {"n_genes": self.G, "hidden": self.h,
-                            "seed": self.cfg.seed, "lr": self.cfg.lr,
-                            "trainer_path": self.cfg.trainer_path,
-                            "world": self.ctx.world, "rank": self.ctx.rank},
-        }
+        blob = {name: (t.cpu() if t is not None else None)
+                for name, t in zip(EPOCH_TENSORS, _epoch_tensors(st))}
+        blob.update(W_keep=st.W_keep.cpu(), t_adam=st.t_adam,
+                    epoch_idx=st.epoch_idx, fingerprint=self._fingerprint())
         blob.update(extra)
         torch.save(blob, path)
 
     def load_train_state(self, st, path: str) -> dict:
         blob = torch.load(path, map_location="cpu", weights_only=False)
-        fp = blob["fingerprint"]
+        fp, mine = blob["fingerprint"], self._fingerprint()
+        # world / rank are recorded for the reader, not compared
         for key in ("n_genes", "hidden", "seed", "lr", "trainer_path"):
-            want = {"n_genes": self.G, "hidden": self.h,
-                    "seed": self.cfg.seed, "lr": self.cfg.lr,
-                    "trainer_path": self.cfg.trainer_path}[key]
-            if fp[key] != want:
+            if fp[key] != mine[key]:
                 raise ValueError(
                     f"--resume-train checkpoint mismatch: {key} was "
-                    f"{fp[key]}, this run has {want}")
-        st.W.copy_(blob["W"].to(self.device))
-        st.who.copy_(blob["who"].to(self.device))
-        st.mW.copy_(blob["mW"].to(self.device))
-        st.vW.copy_(blob["vW"].to(self.device))
-        st.mO.copy_(blob["mO"].to(self.device))
-        st.vO.copy_(blob["vO"].to(self.device))
-        st.W_keep.copy_(blob["W_keep"].to(self.device))
-        if st.dO_buf is not None and blob["dO_buf"] is not None:
-            st.dO_buf.copy_(blob["dO_buf"].to(self.device))
+                    f"{fp[key]}, this run has {mine[key]}")
+        for name, dst in zip(EPOCH_TENSORS + ("W_keep",),
+                             _epoch_tensors(st) + (st.W_keep,)):
+            if dst is not None and blob[name] is not None:
+                dst.copy_(blob[name].to(self.device))
         st.t_adam = int(blob["t_adam"])
         st.epoch_idx = int(blob["epoch_idx"])
         if st.s_buf is not None:        # derived: recompute from W, who
             ops.gemv_rows(st.W, st.who, st.s_buf)
         return blob
 
+    # ------------------------------------------------------------------ train
     def train(self, ps: PathSet, pre_sharded: bool = False) -> TrainResult:
+        """The one driver: resume if asked, pick a runner, report."""
         cfg = self.cfg
         st = self.setup(ps, pre_sharded)
+
+        def rank_path(p: str) -> str:
+            # dO_buf / split shards are rank-local: world>1 checkpoints
+            # are one file per rank
+            return p if self.ctx.world == 1 else f"{p}.rank{self.ctx.rank}"
+
+        trk = StopTracker(cfg.early_stop)
+        if cfg.resume_train:
+            blob = self.load_train_state(st, rank_path(cfg.resume_train))
+            trk = StopTracker(cfg.early_stop,
+                              float(blob.get("before_val", -1.0)),
+                              float(blob.get("before_tr", -1.0)),
+                              list(blob.get("acc_hist", [])))
+            self.log(f"    (resumed training state at epoch {st.epoch_idx} "
+                     f"from {cfg.resume_train})")
+        rep = _Reporter(self.log, trk.before_val, trk.before_tr)
 
         ckpting = bool(cfg.train_ckpt) or bool(cfg.resume_train)
         if (not ckpting and
@@ -847,124 +950,27 @@ class CbowTrainer:
             # GPU fast path always; CPU too when --earlystop-every opts
             # into the k-granular runner (the flag must never be a
             # silent no-op — cf. the round-1 --dtype finding).
-            # Train-state checkpointing runs the synchronous loop on any
+            if cfg.early_stop and cfg.earlystop_every > 1:
+                out = self.run_epochs_kgranular(
+                    st, cfg.epochs, cfg.earlystop_every, rep.on_epoch)
+            else:
+                out = self.run_epochs_pipelined(
+                    st, cfg.epochs, cfg.early_stop, rep.on_epoch)
+        else:
+            # Train-state checkpointing runs the synchronous runner on any
             # device: checkpoints must be epoch-aligned, which the
             # speculative pipeline is not.
-            return self._train_pipelined(st)
-
-        before_val, before_tr = -1.0, -1.0
-        stop_epoch = -1
-        acc_hist: List[float] = []
-        epoch_times: List[float] = []
-        wall_to_acc = None
-        start_epoch = 0
-
-        def _rank_path(p: str) -> str:
-            # dO_buf / split shards are rank-local: world>1 checkpoints
-            # are one file per rank
-            return p if self.ctx.world == 1 else f"{p}.rank{self.ctx.rank}"
-
-        if cfg.resume_train:
-            blob = self.load_train_state(st, _rank_path(cfg.resume_train))
-            acc_hist = list(blob.get("acc_hist", []))
-            before_val = float(blob.get("before_val", -1.0))
-            before_tr = float(blob.get("before_tr", -1.0))
-            start_epoch = st.epoch_idx
-            self.log(f"    (resumed training state at epoch {start_epoch} "
-                     f"from {cfg.resume_train})")
-        t0_all = time.perf_counter()
-        display_step = 5
-        blk_t0 = time.perf_counter()
-
-        self.log("     Start training the modified CBOW with early stopping")
-        epochs_run = start_epoch
-        acc_val, acc_tr = before_val, before_tr
-        for epoch in range(start_epoch, cfg.epochs):
-            ep_t0 = time.perf_counter()
-            acc_tr, acc_val = self.run_epoch(st)
-            epochs_run = epoch + 1
-            acc_hist.append(acc_val)
-            epoch_times.append(time.perf_counter() - ep_t0)
-            if wall_to_acc is None and acc_val >= self.ACC_TARGET:
-                wall_to_acc = time.perf_counter() - t0_all
-
-            if epoch % display_step == 0:
-                self.log("    - Epoch: %03d\tACC[val]=%.4f\tACC[tr]=%.4f (%.3f sec)"
-                         % (epoch, acc_val, acc_tr,
-                            time.perf_counter() - blk_t0))
-                blk_t0 = time.perf_counter()
-            if cfg.early_stop and acc_val < before_val:
-                stop_epoch = epoch - 1
-                self.log("    - Epoch(stop): %03d\tACC[val]=%.4f\tACC[tr]=%.4f (%.3f sec)"
-                         % (stop_epoch, before_val, before_tr,
-                            time.perf_counter() - blk_t0))
-                acc_val, acc_tr = before_val, before_tr
-                break
-            before_val, before_tr = acc_val, acc_tr
-            st.W_keep.copy_(st.W)   # keep-last-good snapshot (G2Vec.py:283)
-            if (cfg.train_ckpt and
-                    (epoch + 1) % max(cfg.train_ckpt_every, 1) == 0):
-                self.save_train_state(st, _rank_path(cfg.train_ckpt),
-                                      {"acc_hist": acc_hist,
-                                       "before_val": before_val,
-                                       "before_tr": before_tr})
-        self.log("    Optimization Finish")
-
-        return TrainResult(W_ih=self._unrelabel(st.W_keep),
-                           stop_epoch=stop_epoch,
-                           acc_val=acc_val, acc_tr=acc_tr,
-                           epochs_run=epochs_run, acc_val_history=acc_hist,
-                           epoch_times_s=epoch_times, wall_to_acc_s=wall_to_acc)
-
-    def _train_pipelined(self, st) -> TrainResult:
-        """train() driver over the speculative epoch pipeline (GPU
-        fast-path full batch). Output lines and results match the
-        synchronous loop exactly."""
-        cfg = self.cfg
-        tr_hist: List[float] = []
-        epoch_times: List[float] = []
-        wall_box = [None]
-        t0_all = time.perf_counter()
-        blk = [time.perf_counter()]
-        last = [t0_all]
-
-        self.log("     Start training the modified CBOW with early stopping")
-
-        def on_epoch(e, a_tr, a_val):
-            now = time.perf_counter()
-            epoch_times.append(now - last[0])
-            last[0] = now
-            tr_hist.append(a_tr)
-            if wall_box[0] is None and a_val >= self.ACC_TARGET:
-                wall_box[0] = now - t0_all
-            if e % 5 == 0:
-                self.log("    - Epoch: %03d\tACC[val]=%.4f\tACC[tr]=%.4f (%.3f sec)"
-                         % (e, a_val, a_tr, now - blk[0]))
-                blk[0] = now
-
-        if cfg.early_stop and cfg.earlystop_every > 1:
-            hist, stop_epoch, W_final, _who_final, _ltr = \
-                self.run_epochs_kgranular(st, cfg.epochs,
-                                          cfg.earlystop_every, on_epoch)
-        else:
-            hist, stop_epoch, W_final, _who_final, _ltr = \
-                self.run_epochs_pipelined(st, cfg.epochs, cfg.early_stop,
-                                          on_epoch)
-        epochs_run = len(hist)
-        if stop_epoch >= 0:
-            acc_val, acc_tr = hist[stop_epoch], tr_hist[stop_epoch]
-            self.log("    - Epoch(stop): %03d\tACC[val]=%.4f\tACC[tr]=%.4f (%.3f sec)"
-                     % (stop_epoch, acc_val, acc_tr,
-                        time.perf_counter() - blk[0]))
-        else:
-            acc_val, acc_tr = hist[-1], tr_hist[-1]
-        self.log("    Optimization Finish")
-        return TrainResult(W_ih=self._unrelabel(W_final),
-                           stop_epoch=stop_epoch,
-                           acc_val=acc_val, acc_tr=acc_tr,
-                           epochs_run=epochs_run, acc_val_history=hist,
-                           epoch_times_s=epoch_times,
-                           wall_to_acc_s=wall_box[0])
+            def save_ckpt(epoch, t):
+                if (epoch + 1) % max(cfg.train_ckpt_every, 1) == 0:
+                    self.save_train_state(
+                        st, rank_path(cfg.train_ckpt),
+                        {"acc_hist": t.hist, "before_val": t.before_val,
+                         "before_tr": t.before_tr})
+            out = self.run_epochs_sync(
+                st, cfg.epochs, cfg.early_stop, rep.on_epoch, trk,
+                save_ckpt if cfg.train_ckpt else None)
+        hist, stop_epoch, W_final, _who, _acc_tr = out
+        return rep.finish(self._unrelabel(W_final), hist, stop_epoch)
 
     def _unrelabel(self, W: torch.Tensor) -> torch.Tensor:
         """Rows back to original gene order (no-op when relabeling is off).
@@ -1019,18 +1025,15 @@ class CbowTrainer:
             W16.copy_(W)
 
     def _accuracy(self, W, W16, who, ps: PathSet, n_global: int) -> float:
+        """One split's accuracy on the general path (the fast path counts
+        both splits in its fused eval)."""
         if ps.n_paths == 0:
             correct = torch.zeros((), dtype=torch.float32, device=self.device)
-        elif self.cfg.trainer_path == "general":
+        else:
             Wg = W16 if W16 is not None else W
             _l, corr, _d, _h = ops.cbow_fwd(
                 Wg, who, ps.genes, ps.offsets, ps.labels, 1.0, False,
                 act=1 if self.cfg.activation == "relu" else 0)
-            correct = corr.sum()
-        else:
-            s = torch.mv(W, who)
-            _l, corr, _d = ops.cbow_fwd_scalar(s, ps.genes, ps.offsets,
-                                               ps.labels, 1.0, False)
             correct = corr.sum()
         self.ctx.allreduce_(correct)                # C3 scalar metric reduce
         return float(correct.item()) / max(n_global, 1)

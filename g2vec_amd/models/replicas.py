@@ -24,16 +24,55 @@ from __future__ import annotations
 
 import dataclasses
 import time
-from typing import List
+from typing import Any, List, Optional
 
 import torch
 
 from .. import ops
 from ..config import G2VecConfig
-from .cbow import CbowTrainer, TrainResult
+from ..parallel.dist import single
+from ..paths import PathSet
+from .cbow import CbowTrainer, StopTracker, TrainResult, accuracies
+
+
+@dataclasses.dataclass
+class ReplicaState:
+    """TrainState's batched counterpart: the path-derived pieces are the
+    base state's, the weight-shaped ones carry a leading replica axis."""
+    R: int
+    tr: PathSet
+    vl: PathSet
+    plan: Any
+    inv_b: float
+    ev_genes: Optional[torch.Tensor]
+    ev_offsets: Optional[torch.Tensor]
+    ev_labels: Optional[torch.Tensor]
+    W: torch.Tensor                          # [R, G, h]
+    who: torch.Tensor                        # [R, h]
+    mW: Optional[torch.Tensor] = None
+    vW: Optional[torch.Tensor] = None
+    mO: Optional[torch.Tensor] = None
+    vO: Optional[torch.Tensor] = None
+    W_keep: Optional[torch.Tensor] = None    # only under early stop
+    s_R: Optional[torch.Tensor] = None       # [G, R]
+    dO_R: Optional[torch.Tensor] = None      # [P_tr, R]
+    counts_R: Optional[torch.Tensor] = None  # [R, 2]
+    lrt_buf: Optional[torch.Tensor] = None
+    t_adam: int = 0
+    epoch_idx: int = 0
+    graph: Any = None
+    graph_failed: bool = False
 
 
 class ReplicaTrainer:
+    B1, B2, EPS = CbowTrainer.B1, CbowTrainer.B2, CbowTrainer.EPS
+    # the epoch step and its single-branch hipGraph capture (from the
+    # second epoch on; lr_t is read from its device slot) are the single
+    # trainer's own methods, run on this trainer's batched body: they touch
+    # only device, cfg, ctx, log and _epoch_body_fast
+    _step_epoch = CbowTrainer._step_epoch
+    _ensure_graph = CbowTrainer._ensure_graph
+
     def __init__(self, cfg: G2VecConfig, n_genes: int, device: torch.device,
                  log=print):
         cfg.validate()
@@ -42,6 +81,7 @@ class ReplicaTrainer:
         self.G = n_genes
         self.h = cfg.hidden
         self.device = device
+        self.ctx = single(device)       # replicates are single-process
         self.log = log
 
     # ------------------------------------------------------------------ setup
@@ -78,18 +118,16 @@ class ReplicaTrainer:
         b = self.base.setup(ps)
         self.n_tr, self.n_vl = self.base.n_tr_global, self.base.n_vl_global
         dev, G, h = self.device, self.G, self.h
-        st = type("ReplicaState", (), {})()
-        st.R = R
-        st.tr, st.vl, st.plan, st.inv_b = b.tr, b.vl, b.plan, b.inv_b
-        st.ev_genes, st.ev_offsets = b.ev_genes, b.ev_offsets
-        st.ev_labels = b.ev_labels if b.ev_genes is not None else None
-        st.W = torch.empty(R, G, h, dtype=torch.float32, device=dev)
-        st.who = torch.empty(R, h, dtype=torch.float32, device=dev)
+        st = ReplicaState(
+            R=R, tr=b.tr, vl=b.vl, plan=b.plan, inv_b=b.inv_b,
+            ev_genes=b.ev_genes, ev_offsets=b.ev_offsets,
+            ev_labels=b.ev_labels,
+            W=torch.empty(R, G, h, dtype=torch.float32, device=dev),
+            who=torch.empty(R, h, dtype=torch.float32, device=dev))
         st.W[0].copy_(b.W)
         st.who[0].copy_(b.who)
-        for name in ("W", "mW", "vW", "W_keep"):     # only the shared pieces
-            delattr(b, name)                         # of the base state stay
-        for r in range(1, R):
+        b.W = b.mW = b.vW = b.W_keep = None      # only the shared pieces
+        for r in range(1, R):                    # of the base state stay
             t = CbowTrainer(dataclasses.replace(cfg, seed=seed + r), G, dev,
                             log=quiet)
             gen = torch.Generator()
@@ -108,10 +146,6 @@ class ReplicaTrainer:
                               device=dev)
         st.counts_R = torch.zeros(R, 2, dtype=torch.float32, device=dev)
         st.lrt_buf = torch.zeros(1, dtype=torch.float32, device=dev)
-        st.t_adam = 0
-        st.epoch_idx = 0
-        st.graph = None
-        st.graph_failed = False
         # the pending dlogits of the first step: one eval over the train
         # paths at the initial weights
         ops.gemv_rows_rep_(st.W, st.who, st.s_R)
@@ -123,15 +157,14 @@ class ReplicaTrainer:
         return st
 
     # ------------------------------------------------------------------ epoch
-    def _epoch_body(self, st) -> None:
+    def _epoch_body_fast(self, st) -> None:
         """CbowTrainer._epoch_body_fast, batched: optimizer step at W_t from
         the pending dO_R, then post-update s_R, the accuracy counts and the
         next epoch's dO_R. Persistent buffers only, so it can be captured."""
-        B = CbowTrainer
         lrt = st.lrt_buf if self.device.type == "cuda" else None
         c_R = ops.scatter_dO_rep(st.plan, st.dO_R, self.G)
         ops.adam_rank1_rep(st.W, st.mW, st.vW, c_R, st.who, st.mO, st.vO,
-                           st.t_adam, self.cfg.lr, B.B1, B.B2, B.EPS,
+                           st.t_adam, self.cfg.lr, self.B1, self.B2, self.EPS,
                            lrt_buf=lrt)
         ops.gemv_rows_rep_(st.W, st.who, st.s_R)
         if st.ev_genes is not None:
@@ -140,49 +173,21 @@ class ReplicaTrainer:
                                       st.counts_R, dO_R=st.dO_R,
                                       inv_b=st.inv_b)
 
-    def _ensure_graph(self, st) -> None:
-        """Single-branch hipGraph of the body from the second epoch on, as
-        CbowTrainer._ensure_graph (lr_t is read from its device slot)."""
-        if (self.device.type == "cuda" and self.cfg.use_hipgraph and
-                st.graph is None and not st.graph_failed and
-                st.epoch_idx >= 1):
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._epoch_body(st)
-                st.graph = g
-            except Exception as e:  # noqa: BLE001
-                st.graph_failed = True
-                self.log(f"    (hipGraph capture unavailable: {e!r}; "
-                         f"running eager)")
-
     def run_epoch(self, st):
         """One epoch of all replicas and ONE [R, 2] readback. Returns
         (acc_tr, acc_val), two lists of R floats."""
-        B = CbowTrainer
-        st.t_adam += 1
-        if self.device.type == "cuda":
-            st.lrt_buf.fill_(ops.tf1_lr_t(self.cfg.lr, B.B1, B.B2, st.t_adam))
-            self._ensure_graph(st)
-        if st.graph is not None:
-            st.graph.replay()
-        else:
-            self._epoch_body(st)
-        cc = st.counts_R.cpu().numpy()
-        st.epoch_idx += 1
-        acc_tr = [float(cc[r, 0]) / max(self.n_tr, 1) for r in range(st.R)]
-        acc_val = [float(cc[r, 1]) / max(self.n_vl, 1) for r in range(st.R)]
-        return acc_tr, acc_val
+        self._step_epoch(st)
+        accs = [accuracies(c, self.n_tr, self.n_vl)
+                for c in st.counts_R.cpu().numpy()]
+        return [a[0] for a in accs], [a[1] for a in accs]
 
     # ------------------------------------------------------------------ train
     def train(self, ps, R: int) -> List[TrainResult]:
         cfg = self.cfg
         st = self.setup(ps, R)
         R = st.R
-        before_val, before_tr = [-1.0] * R, [-1.0] * R
-        stop_epoch, epochs_run = [-1] * R, [0] * R
+        trk = [StopTracker(cfg.early_stop) for _ in range(R)]
         stopped = [False] * R
-        hist: List[List[float]] = [[] for _ in range(R)]
         times: List[List[float]] = [[] for _ in range(R)]
         wall: List = [None] * R
         t0_all = time.perf_counter()
@@ -195,16 +200,10 @@ class ReplicaTrainer:
             for r in range(R):
                 if stopped[r]:
                     continue
-                epochs_run[r] = epoch + 1
-                hist[r].append(acc_val[r])
                 times[r].append(now - ep_t0)
                 if wall[r] is None and acc_val[r] >= CbowTrainer.ACC_TARGET:
                     wall[r] = now - t0_all
-                if cfg.early_stop and acc_val[r] < before_val[r]:
-                    stopped[r] = True
-                    stop_epoch[r] = epoch - 1
-                else:
-                    before_val[r], before_tr[r] = acc_val[r], acc_tr[r]
+                stopped[r] = trk[r].feed(epoch, acc_tr[r], acc_val[r])
             if cfg.early_stop:          # keep-last-good, frozen once stopped
                 if not any(stopped):
                     st.W_keep.copy_(st.W)
@@ -216,14 +215,14 @@ class ReplicaTrainer:
                     break
         out = []
         final = st.W_keep if cfg.early_stop else st.W
-        for r in range(R):
+        for r, t in enumerate(trk):
             self.log("    - Replica %02d: Epoch(stop): %03d\tACC[val]=%.4f"
-                     "\tACC[tr]=%.4f" % (r, stop_epoch[r], before_val[r],
-                                         before_tr[r]))
+                     "\tACC[tr]=%.4f" % (r, t.stop_epoch, t.before_val,
+                                         t.before_tr))
             out.append(TrainResult(
-                W_ih=self.base._unrelabel(final[r]), stop_epoch=stop_epoch[r],
-                acc_val=before_val[r], acc_tr=before_tr[r],
-                epochs_run=epochs_run[r], acc_val_history=hist[r],
+                W_ih=self.base._unrelabel(final[r]), stop_epoch=t.stop_epoch,
+                acc_val=t.before_val, acc_tr=t.before_tr,
+                epochs_run=len(t.hist), acc_val_history=t.hist,
                 epoch_times_s=times[r], wall_to_acc_s=wall[r]))
         self.log("    Optimization Finish (%.3f sec)"
                  % (time.perf_counter() - t0_all))

@@ -171,6 +171,52 @@ def test_trainer_relabel_is_undone_per_replica():
         assert torch.equal(rc.bits(res[r].W_ih), rc.bits(ref["W_ih"]))
 
 
+def test_replica0_is_the_single_train_run_and_transcript_stops():
+    """R = 3 on the runner-equivalence Fixture A: replica 0's TrainResult is
+    the single train() result field for field (timings aside), and the
+    transcript's per-replica lines carry the stop epochs of three single
+    runs with seeds 1, 2, 3."""
+    import dataclasses
+    import re
+
+    import runner_cases as rcase
+    from g2vec_amd.models.cbow import CbowTrainer
+    ps, cfg = rcase.fixture("A", early_stop=True)
+    lines = []
+    res = ReplicaTrainer(cfg, ps.n_genes, CPU, log=lines.append).train(ps, 3)
+    single = CbowTrainer(cfg, ps.n_genes, CPU, log=rcase.quiet).train(ps)
+    assert single.stop_epoch >= 8
+    # "the single run with seed + r" is what the replica trainer means by
+    # it: replicas share seed 1's split and differ in the weight seed only
+    # (a train() with seed 2 would also reshuffle the split)
+    singles = [rc.single_sync_run(*rc.single_state(cfg, ps, CPU, r),
+                                  cfg.epochs, True) for r in range(3)]
+    assert singles[0]["stop_epoch"] == single.stop_epoch
+    for f in dataclasses.fields(single):
+        got, want = getattr(res[0], f.name), getattr(single, f.name)
+        if f.name == "W_ih":
+            assert torch.equal(got, want)
+        elif f.name == "epoch_times_s":
+            assert len(got) == len(want) == res[0].epochs_run
+        elif f.name == "wall_to_acc_s":
+            assert (got is None) == (want is None)
+        else:
+            assert got == want, f.name
+    stops = [int(m.group(2)) for m in
+             (re.search(r"- Replica (\d\d): Epoch\(stop\): (-?\d+)\t", ln)
+              for ln in lines) if m]
+    assert stops == [s["stop_epoch"] for s in singles]
+    assert lines[0] == ("     Start training 3 replicates of the modified "
+                        "CBOW with early stopping")
+    assert re.fullmatch(r"    Optimization Finish \(\d+\.\d{3} sec\)",
+                        lines[-1])
+    for r in range(3):
+        assert lines[1 + r] == (
+            "    - Replica %02d: Epoch(stop): %03d\tACC[val]=%.4f"
+            "\tACC[tr]=%.4f" % (r, singles[r]["stop_epoch"],
+                                singles[r]["acc_val"], singles[r]["acc_tr"]))
+
+
 def test_synth_pathset_shape():
     """The benchmark's path sets: ids in range, distinct within a path,
     lengths in [1, len_path], seeded."""
