@@ -56,7 +56,8 @@ def path_hash(genes) -> np.int64:
 # ------------------------------------------------------------------ walks
 def random_walks(row_ptr: torch.Tensor, col_idx: torch.Tensor, weights: torch.Tensor,
                  sources: torch.Tensor, num_repetition: int, len_path: int,
-                 seed: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                 seed: int, *, walk_ids=None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Non-revisiting weighted random walks on a CSR graph.
 
     One walk per (repetition, source), walk_id = rep * n_src + src_pos.
@@ -64,6 +65,9 @@ def random_walks(row_ptr: torch.Tensor, col_idx: torch.Tensor, weights: torch.Te
     Matches the reference walk semantics (G2Vec.py:328-346): the current node
     is appended, all visited nodes (incl. current) are masked to weight 0,
     step chosen proportionally to remaining weights, dead-end breaks.
+
+    walk_ids given: only those walk ids (each in [0, n_walks)) are generated
+    and returned, row k being walk walk_ids[k] of the full run.
     """
     rp = row_ptr.cpu().numpy()
     ci = col_idx.cpu().numpy()
@@ -71,11 +75,18 @@ def random_walks(row_ptr: torch.Tensor, col_idx: torch.Tensor, weights: torch.Te
     src = sources.cpu().numpy()
     n_src = len(src)
     n_walks = n_src * num_repetition
-    nodes = np.full((n_walks, len_path), -1, dtype=np.int32)
-    lengths = np.zeros(n_walks, dtype=np.int32)
-    hashes = np.zeros(n_walks, dtype=np.int64)
+    if walk_ids is None:
+        walk_ids = range(n_walks)
+    else:
+        walk_ids = [int(w) for w in walk_ids]
+        if any(w < 0 or w >= n_walks for w in walk_ids):
+            raise ValueError(f"walk_ids must be in [0, {n_walks})")
+    n_out = len(walk_ids)
+    nodes = np.full((n_out, len_path), -1, dtype=np.int32)
+    lengths = np.zeros(n_out, dtype=np.int32)
+    hashes = np.zeros(n_out, dtype=np.int64)
 
-    for wid in range(n_walks):
+    for row, wid in enumerate(walk_ids):
         rep = wid // n_src
         source = int(src[wid % n_src])
         # RNG keyed on the GLOBAL (source, repetition) so DP-sharded
@@ -117,20 +128,24 @@ def random_walks(row_ptr: torch.Tensor, col_idx: torch.Tensor, weights: torch.Te
                 j = int(np.flatnonzero(wt > 0.0)[-1])
             cur = int(nb[j])
         plen = len(visited)
-        nodes[wid, :plen] = visited
-        lengths[wid] = plen
-        hashes[wid] = path_hash(visited)
+        nodes[row, :plen] = visited
+        lengths[row] = plen
+        hashes[row] = path_hash(visited)
     return (torch.from_numpy(nodes), torch.from_numpy(lengths), torch.from_numpy(hashes))
 
 
 # ------------------------------------------------------------------ K9 init
-def trunc_normal_(out: torch.Tensor, std: float, seed: int) -> None:
+def trunc_normal_(out: torch.Tensor, std: float, seed: int,
+                  start: int = 0) -> None:
     """Counter-based +-2sigma truncated normal, mirroring
     trunc_normal_kernel (g2vec_kernels.hip): element i draws Box-Muller
     normals from its own splitmix64 stream and resamples beyond 2sigma.
     Same streams as the device kernel; the float cos/log tails can differ
     by ulps across libm implementations, so parity tests compare with a
-    small tolerance (plus bounds/moments), not bitwise."""
+    small tolerance (plus bounds/moments), not bitwise.
+
+    start: element k of out draws from stream start + k, i.e. out is the
+    slice [start, start + n) of a longer fill with the same seed."""
     import math
 
     flat = out.view(-1)
@@ -139,7 +154,7 @@ def trunc_normal_(out: torch.Tensor, std: float, seed: int) -> None:
     with np.errstate(over="ignore"):
         for i in range(n):
             state = np.uint64(seed) ^ np.uint64(
-                np.uint64(i) * _SM64_M2 + np.uint64(1))
+                np.uint64(start + i) * _SM64_M2 + np.uint64(1))
             state, _ = splitmix64(state)      # warm draw (kernel parity)
             while True:
                 state, r1 = splitmix64(state)

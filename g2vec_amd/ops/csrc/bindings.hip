@@ -4,6 +4,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdio>
 #include <optional>
 #include <cstring>
@@ -35,6 +36,15 @@ inline void check_i32(const torch::Tensor& t, const char* name) {
 #define CHECK_GPU_CONT(x) check_gpu_cont((x), #x)
 #define CHECK_F32(x) check_f32((x), #x)
 #define CHECK_I32(x) check_i32((x), #x)
+
+// A tensor size or user integer that a kernel receives as a 32-bit int goes
+// through here first: a value that does not fit is refused by name instead
+// of reaching the launch truncated. Called before any allocation or launch.
+inline int int_arg(long long v, const char* name) {
+  TORCH_CHECK(v >= 0 && v <= (long long)INT_MAX, name,
+              " must be in [0, 2^31), got ", v);
+  return (int)v;
+}
 
 inline torch::TensorOptions opts_on(const torch::Tensor& t,
                                     at::ScalarType dtype = at::kFloat) {
@@ -105,8 +115,9 @@ std::vector<torch::Tensor> random_walks(torch::Tensor row_ptr, torch::Tensor col
                                         int64_t seed) {
   CHECK_I32(row_ptr); CHECK_I32(col_idx); CHECK_F32(weights); CHECK_I32(sources);
   TORCH_CHECK(len_path >= 1 && len_path <= 512, "len_path out of range");
-  const long long n_src = sources.numel();
-  const long long n_walks = n_src * num_repetition;
+  const int n_src = int_arg(sources.numel(), "sources.numel()");
+  const int num_rep = int_arg(num_repetition, "num_repetition");
+  const long long n_walks = (long long)n_src * num_rep;
   auto nodes = torch::empty({n_walks, len_path}, opts_on(row_ptr, at::kInt));
   auto lengths = torch::empty({n_walks}, opts_on(row_ptr, at::kInt));
   auto hashes = torch::empty({n_walks}, opts_on(row_ptr, at::kLong));
@@ -119,7 +130,7 @@ std::vector<torch::Tensor> random_walks(torch::Tensor row_ptr, torch::Tensor col
                      cur_stream(), row_ptr.data_ptr<int>(),
                      col_idx.data_ptr<int>(), weights.data_ptr<float>(),
                      sources.data_ptr<int>(),
-                     (int)n_src, n_walks, (int)num_repetition, (int)len_path,
+                     n_src, n_walks, num_rep, (int)len_path,
                      tsize, (uint64_t)seed,
                      nodes.data_ptr<int>(), lengths.data_ptr<int>(),
                      (long long*)hashes.data_ptr<int64_t>());
@@ -265,12 +276,12 @@ void scatter_dO_det_(torch::Tensor inst_path, torch::Tensor seg_start,
   // gathered instead of thrashing across the whole dO table.
   CHECK_I32(inst_path); CHECK_I32(seg_start); CHECK_I32(seg_gene);
   CHECK_F32(dO); CHECK_F32(c);
-  const long long n_seg = seg_gene.numel();
+  const int n_seg = int_arg(seg_gene.numel(), "seg_gene.numel()");
   if (n_seg == 0) return;
   hipLaunchKernelGGL(scatter_do_det_kernel, dim3(grid_for(n_seg, 4)), dim3(256),
                      0, cur_stream(), inst_path.data_ptr<int>(),
                      seg_start.data_ptr<int>(), seg_gene.data_ptr<int>(),
-                     (int)n_seg, dO.data_ptr<float>(), c.data_ptr<float>());
+                     n_seg, dO.data_ptr<float>(), c.data_ptr<float>());
   LAUNCH_CHECK();
 }
 
@@ -303,7 +314,7 @@ void adam_rank1(torch::Tensor W, torch::Tensor m, torch::Tensor v,
   check_lrt(lrt);
   TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long G = W.size(0);
-  const int h = (int)W.size(1);
+  const int h = int_arg(W.size(1), "W.size(1)");
   TORCH_CHECK(h >= 4 && h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
               "hidden must be a multiple of 4 with h/4 dividing 256");
   TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
@@ -368,8 +379,9 @@ std::vector<torch::Tensor> cbow_fwd(torch::Tensor W, torch::Tensor who,
   TORCH_CHECK(bf16 || fp16 || W.scalar_type() == at::kFloat,
               "W must be f32, bf16 or fp16");
   const long long P = labels.numel();
-  const int h = (int)W.size(1);
+  const int h = int_arg(W.size(1), "W.size(1)");
   const int hpl = hpl_for(h);
+  const int act_i = int_arg(act, "act");
   auto loss = torch::empty({P}, opts_on(W));
   auto correct = torch::empty({P}, opts_on(W));
   auto dO = torch::empty({want_grad ? P : 0}, opts_on(W));
@@ -389,7 +401,7 @@ std::vector<torch::Tensor> cbow_fwd(torch::Tensor W, torch::Tensor who,
                          genes.data_ptr<int>(), offs.data_ptr<int>(),
                          labels.data_ptr<float>(), P, (float)inv_b, h, Hp,
                          loss.data_ptr<float>(), correct.data_ptr<float>(),
-                         dOp, (int)act);
+                         dOp, act_i);
       LAUNCH_CHECK();
     });
   };
@@ -407,10 +419,10 @@ torch::Tensor cbow_bwd_rows(torch::Tensor who, torch::Tensor inst_path,
   CHECK_F32(who); CHECK_I32(inst_path); CHECK_I32(seg_start);
   CHECK_I32(seg_gene); CHECK_F32(dO);
   if (Hpre) CHECK_F32(*Hpre);
-  const int h = (int)who.numel();
+  const int h = int_arg(who.numel(), "who.numel()");
   const int hpl = hpl_for(h);
+  const int n_seg = int_arg(seg_gene.numel(), "seg_gene.numel()");
   auto dW = torch::zeros({n_genes, h}, opts_on(dO));
-  const int n_seg = (int)seg_gene.numel();
   if (n_seg == 0) return dW;
   const int grid = grid_for(n_seg, 4);
   dispatch_hpl(hpl, [&](auto HPL) {
@@ -430,7 +442,7 @@ torch::Tensor pcc_edges(torch::Tensor zt, torch::Tensor edge_idx,
                         int64_t n_group) {
   CHECK_F32(zt); CHECK_I32(edge_idx);
   const long long E = edge_idx.size(0);
-  const int S = (int)zt.size(1);
+  const int S = int_arg(zt.size(1), "zt.size(1)");
   auto out = torch::empty({E}, opts_on(zt));
   if (E == 0) return out;
   hipLaunchKernelGGL(pcc_edges_kernel, dim3(grid_for(E, 4)), dim3(256), 0,
@@ -455,15 +467,21 @@ torch::Tensor corr_gemm(torch::Tensor zt, int64_t n_group) {
                 "corr_gemm: MFMA kernel is gfx950-only, device reports ",
                 prop.gcnArchName, " (use pcc_mode=edge)");
   }
-  const int G = (int)zt.size(0);
-  const int S = (int)zt.size(1);
+  const int G = int_arg(zt.size(0), "zt.size(0)");
+  const int S = int_arg(zt.size(1), "zt.size(1)");
+  // one block per 64 x 64 tile of C: the tile count is the launch's grid.x
+  const long long ntile = ((long long)G + 63) / 64;
+  TORCH_CHECK(ntile * ntile <= (long long)INT_MAX, "corr_gemm: zt.size(0) = ",
+              G, " needs ", ntile * ntile,
+              " tiles, over the 2^31 - 1 blocks of one launch "
+              "(use pcc_mode=edge)");
   const int S4 = ((S + 3) / 4) * 4;
   const size_t lds = 2ull * 64 * S4 * sizeof(float);
   TORCH_CHECK(lds <= 160 * 1024,
               "corr_gemm: S too large for the LDS-staged tile (use pcc_mode=edge)");
   auto C = torch::empty({G, G}, opts_on(zt));
-  const int ntile = (G + 63) / 64;
-  hipLaunchKernelGGL(corr_gemm_kernel, dim3(ntile * ntile), dim3(256), lds,
+  hipLaunchKernelGGL(corr_gemm_kernel, dim3((unsigned)(ntile * ntile)),
+                     dim3(256), lds,
                      cur_stream(), zt.data_ptr<float>(), C.data_ptr<float>(),
                      G, S, S4, 1.0f / (float)n_group);
   LAUNCH_CHECK();
@@ -483,7 +501,7 @@ void trunc_normal_(torch::Tensor out, double std, int64_t seed) {
 void gemv_rows_(torch::Tensor W, torch::Tensor x, torch::Tensor out) {
   CHECK_F32(W); CHECK_F32(x); CHECK_F32(out);
   const long long G = W.size(0);
-  const int h = (int)W.size(1);
+  const int h = int_arg(W.size(1), "W.size(1)");
   const int hpl = hpl_for(h);
   TORCH_CHECK(out.numel() == G && x.numel() == h, "gemv_rows shape mismatch");
   int grid = grid_for(G, 4);
@@ -499,16 +517,14 @@ void gemv_rows_(torch::Tensor W, torch::Tensor x, torch::Tensor out) {
 void gemv_cols_(torch::Tensor W, torch::Tensor c, torch::Tensor out) {
   CHECK_F32(W); CHECK_F32(c); CHECK_F32(out);
   const long long G = W.size(0);
-  const int h = (int)W.size(1);
+  const int h = int_arg(W.size(1), "W.size(1)");
   const int cpt = (h >= 256) ? h / 256 : 1;
   TORCH_CHECK(h % 64 == 0 && cpt >= 1 && cpt <= 4 && (cpt & (cpt - 1)) == 0,
               "gemv_cols needs hidden 64*k with h/256 in {<=1,2,4}");
   TORCH_CHECK(out.numel() == h && c.numel() == G, "gemv_cols shape mismatch");
   // ~8 rows per block: small G must still spread over the chip (8 blocks
   // for G=7.5k measured 78 us of serial row-walking; 941 blocks ~10 us)
-  int grid = (int)((G + 7) / 8);
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) grid = 1;
+  const int grid = grid_for(G, 8) > 2048 ? 2048 : grid_for(G, 8);
   auto partials = torch::empty({grid, h}, opts_on(W));
   dispatch_cpt(cpt, [&](auto CPT) {
     hipLaunchKernelGGL((gemv_cols_kernel<decltype(CPT)::value>), dim3(grid),
@@ -603,9 +619,9 @@ void scatter_dO_rep_(torch::Tensor inst_path, torch::Tensor seg_start,
   CHECK_I32(inst_path); CHECK_I32(seg_start); CHECK_I32(seg_gene);
   const int R = check_rep_table(dO_R, "dO_R");
   TORCH_CHECK(check_rep_table(c_R, "c_R") == R, "c_R and dO_R differ in R");
-  const long long n_seg = seg_gene.numel();
+  const int n_seg = int_arg(seg_gene.numel(), "seg_gene.numel()");
   if (n_seg == 0) return;
-  TORCH_CHECK(seg_start.numel() == n_seg + 1,
+  TORCH_CHECK(seg_start.numel() == (long long)n_seg + 1,
               "seg_start must have n_seg + 1 elements");
   // dO_R decides VEC for both tables: c_R rows are written per lane
   dispatch_rep(R, dO_R.data_ptr<float>(), [&](auto NT, auto VEC) {
@@ -613,7 +629,7 @@ void scatter_dO_rep_(torch::Tensor inst_path, torch::Tensor seg_start,
         (scatter_do_rep_kernel<decltype(NT)::value, decltype(VEC)::value>),
         dim3(grid_for(n_seg, 4)), dim3(256), 0, cur_stream(),
         inst_path.data_ptr<int>(), seg_start.data_ptr<int>(),
-        seg_gene.data_ptr<int>(), (int)n_seg, dO_R.data_ptr<float>(), R,
+        seg_gene.data_ptr<int>(), n_seg, dO_R.data_ptr<float>(), R,
         c_R.data_ptr<float>());
     LAUNCH_CHECK();
   });
@@ -631,7 +647,7 @@ void adam_rank1_rep(torch::Tensor W, torch::Tensor m, torch::Tensor v,
   const int R = check_rep_table(c_R, "c_R");
   TORCH_CHECK(W.dim() == 3 && W.size(0) == R, "W must be [R, G, h]");
   const long long G = W.size(1);
-  const int h = (int)W.size(2);
+  const int h = int_arg(W.size(2), "W.size(2)");
   TORCH_CHECK(h >= 4 && h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
               "hidden must be a multiple of 4 with h/4 dividing 256");
   TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
@@ -665,7 +681,7 @@ void gemv_rows_rep_(torch::Tensor W, torch::Tensor who, torch::Tensor s_R) {
   const int R = check_rep_table(s_R, "s_R");
   TORCH_CHECK(W.dim() == 3 && W.size(0) == R, "W must be [R, G, h]");
   const long long G = W.size(1);
-  const int h = (int)W.size(2);
+  const int h = int_arg(W.size(2), "W.size(2)");
   const int hpl = hpl_for(h);
   TORCH_CHECK(s_R.size(0) == G && who.numel() == (long long)R * h,
               "gemv_rows_rep shape mismatch");
@@ -722,7 +738,7 @@ void kmeans_step(torch::Tensor X, torch::Tensor C, torch::Tensor prev,
   CHECK_F64(inertia);
   TORCH_CHECK(X.dim() == 2 && C.dim() == 2, "X must be [G, h] and C [k, h]");
   const long long G = X.size(0);
-  const int h = (int)X.size(1);
+  const int h = int_arg(X.size(1), "X.size(1)");
   const int hpl = hpl_for(h);
   const long long k = C.size(0);
   TORCH_CHECK(C.size(1) == h, "C must have X's ", h, " columns");
@@ -781,7 +797,7 @@ void kmeans_mind2_(torch::Tensor X, torch::Tensor c, torch::Tensor d2) {
   CHECK_F32(X); CHECK_F32(c); CHECK_F32(d2);
   TORCH_CHECK(X.dim() == 2, "X must be [G, h]");
   const long long G = X.size(0);
-  const int h = (int)X.size(1);
+  const int h = int_arg(X.size(1), "X.size(1)");
   const int hpl = hpl_for(h);
   TORCH_CHECK(c.numel() == h, "c must have one element per X column");
   TORCH_CHECK(d2.numel() == G, "d2 must have one element per X row");
@@ -802,7 +818,7 @@ void row_norms_(torch::Tensor W, torch::Tensor out) {
   CHECK_F32(W); CHECK_F32(out);
   TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long G = W.size(0);
-  const int h = (int)W.size(1);
+  const int h = int_arg(W.size(1), "W.size(1)");
   const int hpl = hpl_for(h);
   TORCH_CHECK(out.numel() == G, "out must have one element per W row");
   CHECK_ROWS16(W);

@@ -4,10 +4,15 @@ Inputs are small integers or dyadic values (tests/kernel_edges.py), so
 every reduction is exact in fp32 in any order and the kernel must equal
 the fp64 reference BITWISE. Tolerances remain only behind expf / log1pf /
 sqrtf (loss 1e-5, dO 1e-7 at inv_b = 1/500, Adam 1e-6 / 1e-7 / 1e-7),
-measured against fp64. Shapes are the smallest that take the second
-grid-stride iteration, the unrolled loops and every template
-instantiation. All tests need an MI355X (marked gpu); the CPU twins that
-validate these inputs live in test_kernel_edges_cpu.py."""
+measured against fp64. Shapes are the smallest that take the unrolled
+loops, every template instantiation and, for the launches with a grid cap
+of their own (cbow_fwd_scalar and the eval kernels at 2048 blocks or their
+env knob, the fused adam_rank1 at 1024, gemv_rows at 8192, gemv_cols at
+2048), the second grid-stride iteration. The launches sized by grid_for
+alone (walks, pcc_edges, cbow_fwd, trunc_normal, bf16_copy, adam_dense)
+start a second sweep only past 2^20 blocks: test_gpu_scale.py covers
+that. All tests need an MI355X (marked gpu); the CPU twins that validate
+these inputs live in test_kernel_edges_cpu.py."""
 import pytest
 import torch
 
