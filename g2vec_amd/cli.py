@@ -103,6 +103,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "RESULT_NAME_stability.txt and "
                         "RESULT_NAME_consensus_biomarkers.txt report which "
                         "genes survive the change of seed (1..32; 1 = off)")
+    p.add_argument("--corr", choices=["pearson", "spearman"],
+                   default="pearson",
+                   help="edge weights of the per-group graphs: |Pearson| or "
+                        "|Spearman| (Pearson of the within-group average "
+                        "ranks, ties included)")
+    p.add_argument("--score-stat", choices=["t", "ranksum"], default="t",
+                   help="expression score of step 6: pooled |t| or the "
+                        "Wilcoxon rank-sum |z| (the scores table then holds "
+                        "z_ranksum and auc; --permutations gives the exact "
+                        "permutation rank-sum p-values)")
     p.add_argument("--save-paths", type=str, default="")
     p.add_argument("--load-model", type=str, default="",
                    help="skip training: load W_ih from a --save-model .pt "
@@ -138,7 +148,7 @@ def args_to_config(a: argparse.Namespace) -> G2VecConfig:
         write_scores=a.write_scores or a.permutations > 0,
         permutations=a.permutations, perm_seed=a.perm_seed,
         neighbors=a.neighbors, neighbors_of=a.neighbors_of,
-        replicates=a.replicates)
+        replicates=a.replicates, corr=a.corr, score_stat=a.score_stat)
 
 
 def main(argv=None) -> int:

@@ -112,6 +112,17 @@ class G2VecConfig:
                                     # (models/replicas.py, stability.py);
                                     # 1 = off
 
+    corr: str = dataclasses.field(default="pearson", repr=False)
+                                    # edge weights of step 2b: "pearson" |
+                                    # "spearman" (|Pearson| of the within-
+                                    # group average ranks, ops.rank_columns)
+    score_stat: str = dataclasses.field(default="t", repr=False)
+                                    # step 6's expression score: "t" (pooled
+                                    # |t|) | "ranksum" (Wilcoxon rank-sum |z|,
+                                    # tie-corrected; the scores table then
+                                    # carries z_ranksum and auc, and
+                                    # --permutations runs on the ranks)
+
     def check_replicate_scope(self) -> None:
         """The batched trainer covers the default training regime only; any
         other option is an error that names it, never a silent no-op."""
@@ -189,6 +200,14 @@ class G2VecConfig:
             raise ValueError("neighbors must be in [0, 64] (0 = off)")
         if self.neighbors_of not in ("biomarkers", "all"):
             raise ValueError(f"bad neighbors_of {self.neighbors_of}")
+        if self.corr not in ("pearson", "spearman"):
+            raise ValueError(f"bad corr {self.corr}")
+        if self.score_stat not in ("t", "ranksum"):
+            raise ValueError(f"bad score_stat {self.score_stat}")
+        if self.corr != "pearson" and self.load_paths:
+            raise ValueError(
+                f"corr={self.corr} conflicts with load_paths: the cached "
+                f"paths were walked on a graph this run does not build")
         if not 1 <= self.replicates <= 32:
             raise ValueError("replicates must be in [1, 32] (1 = off)")
         if self.replicates > 1:

@@ -28,10 +28,21 @@ class CsrGraph(NamedTuple):
     n_nodes: int
 
 
-def zscore_group(expr: torch.Tensor, labels: torch.Tensor, group: int) -> torch.Tensor:
+CORR_KINDS = ("pearson", "spearman")
+
+
+def zscore_group(expr: torch.Tensor, labels: torch.Tensor, group: int,
+                 corr: str = "pearson") -> torch.Tensor:
     """f32 [G, S_group] z-scored transposed expression for one group.
-    std is population std (ddof=0) to match np.ndarray.std() in G2Vec.py:356."""
+    std is population std (ddof=0) to match np.ndarray.std() in G2Vec.py:356.
+    corr="spearman": the group's rows are replaced by their within-group
+    average ranks first (ops.rank_columns), so every correlation downstream
+    is Spearman's rho, ties included."""
+    if corr not in CORR_KINDS:
+        raise ValueError(f"corr must be pearson|spearman, got {corr}")
     X = expr[labels == group].float()          # [Sg, G]
+    if corr == "spearman" and X.shape[0] > 0:
+        X = ops.rank_columns(X.contiguous())
     mean = X.mean(dim=0)
     std = X.std(dim=0, unbiased=False)
     z = (X - mean) / torch.where(std > 0, std, torch.ones_like(std))
@@ -72,10 +83,14 @@ def dedupe_edges(edge_idx: torch.Tensor, n_genes: int) -> torch.Tensor:
 def build_group_graph(expr: torch.Tensor, labels: torch.Tensor, group: int,
                       edge_idx: torch.Tensor, n_genes: int,
                       threshold: float = 0.5, mode: str = "auto",
-                      edges_deduped: bool = False) -> CsrGraph:
+                      edges_deduped: bool = False,
+                      corr: str = "pearson") -> CsrGraph:
     """CSR graph for one prognosis group (the sparse equivalent of
     construct_adjMat, G2Vec.py:370-391). edges_deduped=True skips the
-    per-call unique pass (callers hoist dedupe_edges once per dataset)."""
+    per-call unique pass (callers hoist dedupe_edges once per dataset).
+    corr: "pearson" | "spearman" (see zscore_group)."""
+    if corr not in CORR_KINDS:
+        raise ValueError(f"corr must be pearson|spearman, got {corr}")
     device = expr.device
     if edge_idx.numel() == 0:
         return CsrGraph(torch.zeros(n_genes + 1, dtype=torch.int32, device=device),
@@ -85,7 +100,7 @@ def build_group_graph(expr: torch.Tensor, labels: torch.Tensor, group: int,
              else dedupe_edges(edge_idx, n_genes))
     src, dst = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
 
-    zt = zscore_group(expr, labels, group)
+    zt = zscore_group(expr, labels, group, corr)
     w = edge_pcc_weights(zt, pairs, mode)
     keep = w > threshold
     src, dst, w = src[keep], dst[keep], w[keep]

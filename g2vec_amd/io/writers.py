@@ -67,10 +67,13 @@ def write_scores(result_name: str, genes: Sequence[str],
     (the within-L-group 0.5*(minmax d + minmax t) the selection ranks by; NA
     outside L-groups 0 and 1), biomarker (0/1) and, with perm (the dict of
     scoring.permutation_pvalues), p_perm, q_bh, p_maxT. Scores are printed
-    %.6f, p-values %.6g."""
+    %.6f, p-values %.6g. When scores carries "auc" (the rank-sum statistic
+    was scored), the t_score column is named z_ranksum and auc follows it."""
     out = result_name + "_scores.txt"
-    cols = ["GeneSymbol", "Lgroup", "d_score", "t_score", "gene_score",
-            "biomarker"]
+    ranksum = "auc" in scores
+    cols = ["GeneSymbol", "Lgroup", "d_score"] + (
+        ["z_ranksum", "auc"] if ranksum else ["t_score"]) + [
+        "gene_score", "biomarker"]
     if perm is not None:
         cols += ["p_perm", "q_bh", "p_maxT"]
     gs = np.asarray(scores["gene_score"], dtype=np.float64)
@@ -79,7 +82,8 @@ def write_scores(result_name: str, genes: Sequence[str],
         for i, gene in enumerate(genes):
             row = [str(gene), "%d" % int(lgroup_idx[i]),
                    "%.6f" % float(scores["d_score"][i]),
-                   "%.6f" % float(scores["t_score"][i]),
+                   "%.6f" % float(scores["t_score"][i])] + (
+                   ["%.6f" % float(scores["auc"][i])] if ranksum else []) + [
                    "NA" if np.isnan(gs[i]) else "%.6f" % gs[i],
                    "%d" % int(scores["is_biomarker"][i])]
             if perm is not None:

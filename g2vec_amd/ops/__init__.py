@@ -445,6 +445,82 @@ def t_scores(expr, labels) -> torch.Tensor:
     return cpu_ref.t_scores(expr, labels)
 
 
+# ------------------------------------------------------------------ rank statistics
+# Tile constants of rank_body (g2vec_kernels.hip), for the tests' edge
+# shapes: genes per block tile, samples per staged j-tile, x_i per wave,
+# waves per block, and the grid cap beyond which gene tiles are strided.
+RANK_TG = 64
+RANK_SJ = 128
+RANK_IB = 8
+RANK_WAVES = 4
+RANK_MAX_BLOCKS = 16384
+RANK_S_MAX = 1 << 23            # half-integer ranks <= S are exact in f32 below
+RANKSUM_S_MAX = (1 << 21) + 1   # 4*SSR <= S^3 / 3 must fit int64
+
+
+def _rank_check(expr, name: str = "X") -> None:
+    if expr.dtype != torch.float32 or expr.dim() != 2:
+        raise ValueError(f"{name} must be a float32 [S, G] tensor")
+    if not expr.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if not 1 <= expr.shape[0] < RANK_S_MAX:
+        raise ValueError(f"{name} needs 1 <= S < 2^23 rows, got "
+                         f"{expr.shape[0]}")
+    # NaN has no rank
+    if bool(torch.isnan(expr).any()):
+        raise ValueError(f"{name} must not hold NaN")
+
+
+def rank_columns(X) -> torch.Tensor:
+    """ranks f32 [S, G]: the average rank (1-based, ties share the mean of
+    their positions) of every element of X f32 [S, G] within its column:
+    less + 0.5 * (equal + 1) with less = #{j : x[j,g] < x[i,g]} and equal =
+    #{j : x[j,g] == x[i,g]}, self included. IEEE compares: -0.0 ties +0.0,
+    +-inf are ordinary values; NaN is refused. Half-integers, exact in f32;
+    a function of the inputs only."""
+    _rank_check(X)
+    if X.is_cuda:
+        out = torch.empty_like(X)
+        native().rank_columns_(X, out)
+        return out
+    return cpu_ref.rank_columns(X)
+
+
+def ranksum_scores(expr, labels):
+    """(z, auc) f32 [G]: the Wilcoxon rank-sum test of label 1 (poor)
+    against label 0 (good) per gene column of expr f32 [S, G], labels
+    i32/i64 [S]; rows with any other label are dropped first, as t_scores
+    ignores them. z = |W1 - n1 (S+1)/2| / sqrt(n1 n0 / (S (S-1)) * SSR) with
+    W1 the poor group's rank sum and SSR the squared deviations of the
+    average ranks from (S+1)/2 (tie-corrected, no continuity correction);
+    auc = (W1 - n1 (n1+1)/2) / (n1 n0). z = 0 and auc = 0.5 for a constant
+    gene or a group of fewer than 2 samples. Integer sums, f64 epilogue:
+    bitwise reproducible."""
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError("labels must be an int32/int64 [S] tensor")
+    if labels.device != expr.device:
+        raise ValueError("expr and labels must be on the same device")
+    if expr.dim() != 2 or labels.shape[0] != expr.shape[0]:
+        raise ValueError("labels must have one element per row of expr")
+    keep = (labels == 0) | (labels == 1)
+    if not bool(keep.all()):
+        expr, labels = expr[keep].contiguous(), labels[keep]
+    G = expr.shape[1]
+    if expr.shape[0] == 0:
+        return (torch.zeros(G, dtype=torch.float32, device=expr.device),
+                torch.full((G,), 0.5, dtype=torch.float32,
+                           device=expr.device))
+    _rank_check(expr, "expr")
+    if expr.shape[0] >= RANKSUM_S_MAX:
+        raise ValueError("ranksum_scores needs S <= 2^21 samples")
+    if expr.is_cuda:
+        z = torch.empty(G, dtype=torch.float32, device=expr.device)
+        auc = torch.empty(G, dtype=torch.float32, device=expr.device)
+        native().ranksum_scores_(expr, labels.int().contiguous(), z, auc)
+        return z, auc
+    return cpu_ref.ranksum_scores(expr, labels)
+
+
 # ------------------------------------------------------------------ step 6: permutation null of t
 def _perm_check(expr, masks) -> int:
     """The guards both perm_t entry points share, before any launch; returns

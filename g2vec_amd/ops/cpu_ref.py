@@ -337,6 +337,84 @@ def t_scores(expr: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return t.abs().float()
 
 
+# ------------------------------------------------------------------ rank statistics
+RANK_COL_CHUNK = 1 << 15
+
+
+def rank2_columns(x: np.ndarray) -> np.ndarray:
+    """int64 [S, G]: the doubled average rank R2 = 2*less + equal + 1 of every
+    element within its column of x [S, G] (rank_body's integer). Sort, then
+    the first and last sorted position of each run of equal values: less =
+    first, equal = last - first + 1. IEEE ==, so -0.0 ties +0.0."""
+    x = np.asarray(x)
+    S, G = x.shape
+    out = np.empty((S, G), dtype=np.int64)
+    pos = np.arange(S, dtype=np.int64)[:, None]
+    for lo in range(0, G, RANK_COL_CHUNK):
+        xc = x[:, lo:lo + RANK_COL_CHUNK]
+        order = np.argsort(xc, axis=0, kind="stable")
+        xs = np.take_along_axis(xc, order, axis=0)
+        new = np.ones(xs.shape, dtype=bool)         # a run starts here
+        new[1:] = xs[1:] != xs[:-1]
+        first = np.maximum.accumulate(np.where(new, pos, 0), axis=0)
+        end = np.ones(xs.shape, dtype=bool)         # a run ends here
+        end[:-1] = new[1:]
+        last = np.minimum.accumulate(
+            np.where(end, pos, S - 1)[::-1], axis=0)[::-1]
+        r2 = np.empty(xs.shape, dtype=np.int64)
+        np.put_along_axis(r2, order, first + last + 2, axis=0)
+        out[:, lo:lo + RANK_COL_CHUNK] = r2
+    return out
+
+
+def rank_columns(expr: torch.Tensor) -> torch.Tensor:
+    """ranks f32 [S, G] = less + 0.5 * (equal + 1) per column (NaN-free
+    input; rank_columns_kernel)."""
+    r2 = rank2_columns(expr.numpy())
+    return torch.from_numpy((0.5 * r2).astype(np.float32))
+
+
+def ranksum_sums(expr: torch.Tensor, labels: torch.Tensor
+                 ) -> Tuple[np.ndarray, np.ndarray]:
+    """(2*W1, 4*SSR) int64 [G], the integer sums of ranksum_scores_kernel:
+    sum_i R2_i * m_i and sum_i (R2_i - (S + 1))^2, labels 0/1 only."""
+    r2 = rank2_columns(expr.numpy())
+    m = labels.numpy().astype(np.int64)
+    S = r2.shape[0]
+    w2 = (r2 * m[:, None]).sum(axis=0)
+    d = r2 - (S + 1)
+    return w2, (d * d).sum(axis=0)
+
+
+def ranksum_from_sums(w2: np.ndarray, q4: np.ndarray, n1: int, S: int
+                      ) -> Tuple[np.ndarray, np.ndarray]:
+    """f64 (|z|, auc) from the integer sums: the kernel's epilogue."""
+    n1d, n0d, Sd = float(n1), float(S - n1), float(S)
+    W1 = 0.5 * w2.astype(np.float64)
+    z = np.zeros(w2.shape, dtype=np.float64)
+    auc = np.full(w2.shape, 0.5, dtype=np.float64)
+    if n1 < 2 or S - n1 < 2:
+        return z, auc
+    live = q4 > 0
+    var = n1d * n0d / (Sd * (Sd - 1.0)) * (0.25 * q4.astype(np.float64))
+    z[live] = (np.abs(W1 - 0.5 * n1d * (Sd + 1.0))[live]
+               / np.sqrt(var[live]))
+    auc[live] = ((W1 - 0.5 * n1d * (n1d + 1.0)) / (n1d * n0d))[live]
+    return z, auc
+
+
+def ranksum_scores(expr: torch.Tensor, labels: torch.Tensor
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(|z|, auc) f32 [G] of the Wilcoxon rank-sum test per gene column:
+    int64 sums, the f64 epilogue, one rounding to f32. z = 0 and auc = 0.5
+    for a constant gene or a group of fewer than 2 samples."""
+    w2, q4 = ranksum_sums(expr, labels)
+    S = expr.shape[0]
+    z, auc = ranksum_from_sums(w2, q4, int(labels.sum()), S)
+    return (torch.from_numpy(z.astype(np.float32)),
+            torch.from_numpy(auc.astype(np.float32)))
+
+
 # ------------------------------------------------------------------ step 6: permutation null of t
 def splitmix64_vec(state: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """splitmix64 over a uint64 array: (new_state, random_u64), element by

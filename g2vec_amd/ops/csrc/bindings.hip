@@ -854,15 +854,16 @@ void t_scores_(torch::Tensor expr, torch::Tensor labels, torch::Tensor out) {
 }
 
 // ------------------------------------------- step 6: permutation null of t
-inline void check_gfx950(const char* op) {
+inline void check_gfx950(const char* op, const char* what = "MFMA kernel") {
   // the MFMA body is compiled only for gfx950: elsewhere the launch would be
-  // a no-op leaving the outputs unwritten
+  // a no-op leaving the outputs unwritten (the rank kernels are tuned and
+  // tested for gfx950 alone and refuse other devices the same way)
   hipDeviceProp_t prop;
   int dev = 0;
   (void)hipGetDevice(&dev);
   (void)hipGetDeviceProperties(&prop, dev);
   TORCH_CHECK(std::string(prop.gcnArchName).rfind("gfx950", 0) == 0, op,
-              ": MFMA kernel is gfx950-only, device reports ",
+              ": ", what, " is gfx950-only, device reports ",
               prop.gcnArchName);
 }
 
@@ -954,6 +955,69 @@ void perm_t_counts_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
       Q.data_ptr<double>(), stat_obs.data_ptr<double>(), (int)S, G, B, (int)n1,
       counts.data_ptr<int>(),
       reinterpret_cast<unsigned long long*>(maxstat.data_ptr<double>()));
+  LAUNCH_CHECK();
+}
+
+// ------------------------------------------- rank statistics
+// The guards both rank entry points share; every one runs before the first
+// launch, so a refused call leaves the outputs as they were. Returns the grid.
+inline int rank_check(const char* op, const torch::Tensor& expr,
+                      long long s_limit) {
+  CHECK_F32(expr);
+  TORCH_CHECK(expr.dim() == 2, op, ": expr must be [S, G]");
+  const long long S = expr.size(0);
+  const long long G = expr.size(1);
+  // ranks are half-integers <= S: exact in f32 below 2^23
+  TORCH_CHECK(S >= 1 && S < s_limit, op, " needs 1 <= S < ", s_limit,
+              " samples, got ", S);
+  int_arg(S, "expr.size(0)");
+  check_gfx950(op, "rank kernel");
+  long long blocks = (G + RK_TG - 1) / RK_TG;
+  if (blocks > RK_MAX_BLOCKS) blocks = RK_MAX_BLOCKS;
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
+
+void rank_columns_(torch::Tensor expr, torch::Tensor ranks) {
+  const int grid = rank_check("rank_columns", expr, 1LL << 23);
+  CHECK_F32(ranks);
+  TORCH_CHECK(ranks.dim() == 2 && ranks.size(0) == expr.size(0) &&
+                  ranks.size(1) == expr.size(1),
+              "rank_columns: ranks must have expr's shape");
+  TORCH_CHECK(ranks.device() == expr.device(),
+              "rank_columns: expr and ranks must be on one device");
+  const int S = int_arg(expr.size(0), "expr.size(0)");
+  const long long G = expr.size(1);
+  if (G == 0) return;
+  hipLaunchKernelGGL(rank_columns_kernel, dim3(grid), dim3(256), 0,
+                     cur_stream(), expr.data_ptr<float>(), S, G,
+                     ranks.data_ptr<float>());
+  LAUNCH_CHECK();
+}
+
+void ranksum_scores_(torch::Tensor expr, torch::Tensor labels,
+                     torch::Tensor z, torch::Tensor auc) {
+  // 4 SSR <= S^3 / 3 must fit the kernel's int64 sums
+  const int grid = rank_check("ranksum_scores", expr, (1LL << 21) + 1);
+  CHECK_I32(labels); CHECK_F32(z); CHECK_F32(auc);
+  const int S = int_arg(expr.size(0), "expr.size(0)");
+  const long long G = expr.size(1);
+  TORCH_CHECK(labels.dim() == 1 && labels.numel() == S,
+              "ranksum_scores: labels must have one element per sample");
+  TORCH_CHECK(z.dim() == 1 && z.numel() == G && auc.dim() == 1 &&
+                  auc.numel() == G,
+              "ranksum_scores: z and auc must be [G]");
+  TORCH_CHECK(labels.device() == expr.device() &&
+                  z.device() == expr.device() && auc.device() == expr.device(),
+              "ranksum_scores: all tensors must be on one device");
+  TORCH_CHECK(labels.min().item<int>() >= 0 && labels.max().item<int>() <= 1,
+              "ranksum_scores: labels must hold only 0 and 1");
+  const int n1 = int_arg(labels.sum().item<int64_t>(), "sum(labels)");
+  if (G == 0) return;
+  hipLaunchKernelGGL(ranksum_scores_kernel, dim3(grid), dim3(256), 0,
+                     cur_stream(), expr.data_ptr<float>(),
+                     labels.data_ptr<int>(), S, G, n1, z.data_ptr<float>(),
+                     auc.data_ptr<float>());
   LAUNCH_CHECK();
 }
 
@@ -1196,6 +1260,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "t^2 per (relabelling, gene), MFMA f32 (out-arg)");
   m.def("perm_t_counts_", &perm_t_counts_,
         "per-gene exceed counts + per-relabelling max t^2 (out-args)");
+  m.def("rank_columns_", &rank_columns_, py::arg("expr"), py::arg("ranks"),
+        "average ranks per gene column, ties included (out-arg)");
+  m.def("ranksum_scores_", &ranksum_scores_, py::arg("expr"),
+        py::arg("labels"), py::arg("z"), py::arg("auc"),
+        "rank-sum |z| and AUC per gene column (out-args)");
+  m.attr("RK_TG") = RK_TG;
+  m.attr("RK_SJ") = RK_SJ;
+  m.attr("RK_IB") = RK_IB;
+  m.attr("RK_WAVES") = RK_WAVES;
+  m.attr("RK_MAX_BLOCKS") = RK_MAX_BLOCKS;
   m.def("knn_grid_y", &knn_grid_y, py::arg("Q"), py::arg("G"),
         py::arg("grid_y") = 0, "candidate-split block count of knn_topk_");
   m.def("knn_topk_", &knn_topk_, py::arg("Xq"), py::arg("X"),

@@ -33,6 +33,8 @@
 //   kmeans_mind2_kernel<HPL>    (step 5) k-means++ support: d2 = min(d2, |x - c|^2)
 //   row_norms_kernel<HPL>       (step 6) d-score: f64-accumulated row L2 norms
 //   t_scores_kernel             (step 6) |pooled t| per gene column, f64 two-pass
+//   rank_columns_kernel         average ranks per gene column (ties included), LDS-tiled pair counting
+//   ranksum_scores_kernel       (step 6) same body: rank-sum |z| and AUC per gene from int64 sums
 //   col_moments_kernel          (step 6) f64 column sums of x and x*x for the permutation null
 //   perm_t_stats_kernel         (step 6) t^2 per (relabelling, gene) on v_mfma_f32_16x16x4_f32
 //   perm_t_counts_kernel        same body: per-gene exceed counts + per-relabelling max, no G x B output
@@ -1726,6 +1728,146 @@ t_scores_kernel(const float* __restrict__ expr, const int* __restrict__ labels,
       out[g] = t;
     }
   }
+}
+
+// ===================================== rank statistics: average ranks, rank sum
+// For gene column g of expr[S, G] and sample i, the doubled average rank is
+// the integer
+//   R2 = 2 * #{j : x_j < x_i} + #{j : x_j == x_i} + 1
+//      = 1 + sum_j ((x_j < x_i) + (x_j <= x_i))          (self included)
+// with IEEE compares (-0.0 ties +0.0, +-inf are ordinary values; NaN is
+// refused by the caller). rank = R2 / 2 is a half-integer <= S: exact in f32
+// for S < 2^23.
+//
+// One body for the two kernels below. A 256-thread block owns RK_TG = 64
+// consecutive genes, lane l of every wave on gene g0 + l, so each sample row
+// piece is one coalesced 256-byte read and no cross-lane step exists. Wave w
+// keeps RK_IB of its own x_i in registers (samples i0 + w * RK_IB + b of the
+// current i-pass of RK_IB * RK_WAVES samples) and walks j over a
+// [RK_SJ samples][RK_TG genes] LDS tile: tile[j * RK_TG + lane] is one
+// conflict-free ds_read_b32 that feeds RK_IB compare pairs. S is arbitrary:
+// a column longer than RK_SJ is walked j-tile by j-tile, re-staged for every
+// i-pass (the re-read hits L2: 1 staged element per RK_IB * RK_WAVES pair
+// tests); a column that fits is staged once per gene tile. 32 KiB of LDS per
+// block. Gene tiles are grid-strided.
+//
+// SCORES = false writes ranks[i, g] = 0.5f * R2.
+// SCORES = true writes no ranks: per gene it sums, as 64-bit INTEGERS,
+//   w2 = sum_i R2_i * m_i         ( = 2 W1, m = labels, 0/1 only)
+//   q4 = sum_i (R2_i - (S + 1))^2 ( = 4 SSR, tie-corrected by construction)
+// per wave, folds the RK_WAVES partials through LDS (integer adds: any order
+// gives the same bits) and finishes in f64 with one rounding to f32:
+//   z   = |w2/2 - n1 (S+1)/2| / sqrt(n1 n0 / (S (S-1)) * q4/4)
+//   auc = (w2/2 - n1 (n1+1)/2) / (n1 n0)
+// z = 0 and auc = 0.5 when q4 == 0 or a group has fewer than 2 samples (the
+// rule of t_scores_kernel). q4 <= S^3 / 3 fits int64 for S <= 2^21, which the
+// binding enforces for this entry point.
+#define RK_TG 64                   // genes per block tile (one wave wide)
+#define RK_SJ 128                  // samples per staged j-tile
+#define RK_IB 8                    // x_i held in registers per wave
+#define RK_WAVES 4
+#define RK_MAX_BLOCKS 16384        // grid cap; further gene tiles are strided
+
+template <bool SCORES>
+__device__ __forceinline__ void rank_body(
+    const float* __restrict__ expr, const int* __restrict__ labels, int S,
+    long long G, int n1, float* __restrict__ ranks, float* __restrict__ z,
+    float* __restrict__ auc) {
+  __shared__ float tile[RK_SJ * RK_TG];
+  __shared__ long long fold[SCORES ? 2 * RK_WAVES * RK_TG : 1];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = uni(threadIdx.x >> 6);
+  const bool one_tile = S <= RK_SJ;
+  const long long n_gt = (G + RK_TG - 1) / RK_TG;
+  for (long long gt = blockIdx.x; gt < n_gt; gt += gridDim.x) {
+    const long long g = gt * RK_TG + lane;
+    const bool act = g < G;
+    const long long gc = act ? g : G - 1;      // dead lanes re-read the last gene
+    long long w2 = 0, q4 = 0;
+    for (int i0 = 0; i0 < S; i0 += RK_IB * RK_WAVES) {
+      const int iw = i0 + w * RK_IB;           // this wave's first sample
+      float xi[RK_IB];
+      int r2[RK_IB];
+#pragma unroll
+      for (int b = 0; b < RK_IB; ++b) {
+        const int ic = (iw + b < S) ? iw + b : S - 1;
+        G2V_ASSERT(ic >= 0 && ic < S && gc >= 0 && gc < G);
+        xi[b] = expr[(long long)ic * G + gc];
+        r2[b] = 1;
+      }
+      for (int t0 = 0; t0 < S; t0 += RK_SJ) {
+        const int nt = (S - t0 < RK_SJ) ? S - t0 : RK_SJ;
+        if (!one_tile || i0 == 0) {
+          __syncthreads();                     // readers of the last tile done
+          for (int j = w; j < nt; j += RK_WAVES) {
+            G2V_ASSERT(t0 + j < S && j * RK_TG + lane < RK_SJ * RK_TG);
+            tile[j * RK_TG + lane] = expr[(long long)(t0 + j) * G + gc];
+          }
+          __syncthreads();
+        }
+        if (iw < S) {                          // wave-uniform
+#pragma unroll 4
+          for (int j = 0; j < nt; ++j) {
+            const float v = tile[j * RK_TG + lane];
+#pragma unroll
+            for (int b = 0; b < RK_IB; ++b)
+              r2[b] += (int)(v < xi[b]) + (int)(v <= xi[b]);
+          }
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < RK_IB; ++b) {
+        const int i = iw + b;
+        if (i < S) {                           // wave-uniform
+          G2V_ASSERT(r2[b] >= 2 && r2[b] <= 2 * S);
+          if (SCORES) {
+            const long long d = (long long)r2[b] - ((long long)S + 1);
+            w2 += labels[i] ? (long long)r2[b] : 0LL;
+            q4 += d * d;
+          } else if (act) {
+            ranks[(long long)i * G + g] = 0.5f * (float)r2[b];
+          }
+        }
+      }
+    }
+    if (SCORES) {
+      __syncthreads();                         // the last fold's reader is done
+      fold[w * RK_TG + lane] = w2;
+      fold[(RK_WAVES + w) * RK_TG + lane] = q4;
+      __syncthreads();
+      if (w == 0 && act) {
+        long long W2 = 0, Q4 = 0;
+#pragma unroll
+        for (int k = 0; k < RK_WAVES; ++k) {
+          W2 += fold[k * RK_TG + lane];
+          Q4 += fold[(RK_WAVES + k) * RK_TG + lane];
+        }
+        const double n1d = (double)n1, n0d = (double)(S - n1), Sd = (double)S;
+        float zf = 0.f, af = 0.5f;
+        if (Q4 > 0 && n1 >= 2 && S - n1 >= 2) {
+          const double W1 = 0.5 * (double)W2;
+          const double var = n1d * n0d / (Sd * (Sd - 1.0)) * (0.25 * (double)Q4);
+          zf = (float)(fabs(W1 - 0.5 * n1d * (Sd + 1.0)) / sqrt(var));
+          af = (float)((W1 - 0.5 * n1d * (n1d + 1.0)) / (n1d * n0d));
+        }
+        z[g] = zf;
+        auc[g] = af;
+      }
+    }
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+rank_columns_kernel(const float* __restrict__ expr, int S, long long G,
+                    float* __restrict__ ranks) {
+  rank_body<false>(expr, nullptr, S, G, 0, ranks, nullptr, nullptr);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+ranksum_scores_kernel(const float* __restrict__ expr,
+                      const int* __restrict__ labels, int S, long long G,
+                      int n1, float* __restrict__ z, float* __restrict__ auc) {
+  rank_body<true>(expr, labels, S, G, n1, nullptr, z, auc);
 }
 
 // ============================== step 6: label-permutation null of the pooled t

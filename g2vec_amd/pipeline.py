@@ -65,7 +65,7 @@ def generate_paths(cfg: G2VecConfig, expr_t: torch.Tensor, labels_t: torch.Tenso
                                           edge_idx_t, n_genes,
                                           threshold=cfg.pcc_threshold,
                                           mode=cfg.pcc_mode,
-                                          edges_deduped=True)
+                                          edges_deduped=True, corr=cfg.corr)
                     graphs[group] = g
                     raw[group] = generate_walks(g, cfg.len_path,
                                                 cfg.num_repetition, seed,
@@ -81,7 +81,8 @@ def generate_paths(cfg: G2VecConfig, expr_t: torch.Tensor, labels_t: torch.Tenso
             with timers.phase(f"graph_g{group}"):
                 g = build_group_graph(expr_t, labels_t, group, edge_idx_t,
                                       n_genes, threshold=cfg.pcc_threshold,
-                                      mode=cfg.pcc_mode, edges_deduped=True)
+                                      mode=cfg.pcc_mode, edges_deduped=True,
+                                      corr=cfg.corr)
             with timers.phase(f"walks_g{group}"):
                 ws = generate_walks(g, cfg.len_path, cfg.num_repetition, seed,
                                     group, (lo, hi))
@@ -139,6 +140,9 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
 
     log(">>> 3. Generate random paths from each group")
     log("    *** most time consuming step ***")
+    if cfg.corr != "pearson":
+        log("    corr    : %s" % cfg.corr)
+        jsonl.emit("corr", corr=cfg.corr)
     if cfg.load_paths:
         blob = torch.load(cfg.load_paths, map_location=device)
         ps = PathSet(blob["genes"], blob["offsets"], blob["labels"], n_genes)
@@ -232,14 +236,32 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
         if cfg.scoring_backend == "device":
             from . import ops
             d_all = ops.row_norms(W_dev).cpu().numpy()
-            t_all = ops.t_scores(expr_t.float().contiguous(),
-                                 labels_t).cpu().numpy()
+            if cfg.score_stat == "t":
+                t_all = ops.t_scores(expr_t.float().contiguous(),
+                                     labels_t).cpu().numpy()
+        auc_all = None
+        if cfg.score_stat == "ranksum":
+            # |z| of the rank-sum test over all genes once, in place of the
+            # t-scores; min-max, the sort and top-N do not change
+            log("    score   : %s" % cfg.score_stat)
+            if cfg.scoring_backend == "device":
+                z_t, auc_t = ops.ranksum_scores(expr_t.float().contiguous(),
+                                                labels_t)
+                t_all, auc_all = z_t.cpu().numpy(), auc_t.cpu().numpy()
+            else:
+                from .scoring import ranksum_scores as host_ranksum
+                t_all, auc_all = host_ranksum(data["expr"],
+                                              np.asarray(data["label"]))
+            jsonl.emit("score_stat", stat=cfg.score_stat,
+                       backend=cfg.scoring_backend)
         scores = perm = None
         if cfg.write_scores:
             scores = score_genes(W, lg, data["expr"], data["label"],
                                  data["gene"], cfg.num_biomarker,
                                  d_all=d_all, t_all=t_all)
             biomarkers = scores["biomarkers"]
+            if auc_all is not None:
+                scores["auc"] = auc_all
         else:
             biomarkers = select_biomarkers(W, lg, data["expr"], data["label"],
                                            data["gene"], cfg.num_biomarker,
@@ -291,7 +313,14 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
             else int(time.time_ns() & 0x7FFFFFFF))
         t0 = time.perf_counter()
         with timers.phase("permutations"):
-            perm = permutation_pvalues(data["expr"], np.asarray(data["label"]),
+            perm_x = data["expr"]
+            if cfg.score_stat == "ranksum":
+                # the pooled t^2 of the ranks is monotone in |W1 - E W1|, so
+                # the same null gives the exact permutation rank-sum p-value
+                from . import ops
+                perm_x = ops.rank_columns(
+                    expr_t.float().contiguous()).cpu().numpy()
+            perm = permutation_pvalues(perm_x, np.asarray(data["label"]),
                                        cfg.permutations, perm_seed,
                                        device=device)
         jsonl.emit("perm", B=cfg.permutations, seed=perm_seed,

@@ -51,6 +51,58 @@ def t_scores(expr: np.ndarray, labels: np.ndarray) -> np.ndarray:
     return np.abs(t).astype(np.float32)
 
 
+def average_ranks(x: np.ndarray) -> np.ndarray:
+    """f64 [S, G] average ranks (1-based; ties share the mean of their
+    positions) of every element within its column of x [S, G]."""
+    x = np.asarray(x)
+    S = x.shape[0]
+    order = np.argsort(x, axis=0, kind="stable")
+    xs = np.take_along_axis(x, order, axis=0)
+    # a run of equal values shares the mean of its first and last position
+    start = np.ones(xs.shape, dtype=bool)
+    start[1:] = xs[1:] != xs[:-1]
+    stop = np.ones(xs.shape, dtype=bool)
+    stop[:-1] = start[1:]
+    pos = np.arange(1, S + 1, dtype=np.float64)[:, None]
+    first = np.maximum.accumulate(np.where(start, pos, 1.0), axis=0)
+    last = np.minimum.accumulate(
+        np.where(stop, pos, float(S))[::-1], axis=0)[::-1]
+    ranks = np.empty(xs.shape, dtype=np.float64)
+    np.put_along_axis(ranks, order, 0.5 * (first + last), axis=0)
+    return ranks
+
+
+def ranksum_scores(expr: np.ndarray, labels: np.ndarray):
+    """(|z|, auc) f32 [G]: Wilcoxon rank-sum test of the poor (label 1)
+    against the good (label 0) samples per gene column; other labels are
+    left out. Normal approximation with the tie-corrected variance and no
+    continuity correction:
+        z = (W1 - n1 (S+1)/2) / sqrt(n1 n0 / (S (S-1)) * SSR)
+    W1 = the poor group's rank sum, SSR = sum (rank - (S+1)/2)^2, and
+    auc = (W1 - n1 (n1+1)/2) / (n1 n0) = U / (n1 n0). z = 0 and auc = 0.5
+    for a constant gene or a group of fewer than 2 samples (the rule of
+    t_scores). Host f64; ops.ranksum_scores is the device counterpart."""
+    labels = np.asarray(labels)
+    keep = (labels == 0) | (labels == 1)
+    x = np.asarray(expr)[keep]
+    m = labels[keep] == 1
+    S, G = x.shape
+    n1 = int(m.sum())
+    n0 = S - n1
+    z = np.zeros(G, dtype=np.float64)
+    auc = np.full(G, 0.5, dtype=np.float64)
+    if n1 < 2 or n0 < 2:
+        return z.astype(np.float32), auc.astype(np.float32)
+    r = average_ranks(x)
+    W1 = r[m].sum(axis=0)
+    SSR = ((r - 0.5 * (S + 1.0)) ** 2).sum(axis=0)
+    live = SSR > 0.0
+    var = n1 * n0 / (S * (S - 1.0)) * SSR[live]
+    z[live] = np.abs(W1[live] - 0.5 * n1 * (S + 1.0)) / np.sqrt(var)
+    auc[live] = (W1[live] - 0.5 * n1 * (n1 + 1.0)) / (float(n1) * n0)
+    return z.astype(np.float32), auc.astype(np.float32)
+
+
 def select_biomarkers(embeddings: np.ndarray, lgroup_idx: np.ndarray,
                       expr: np.ndarray, labels: np.ndarray,
                       genes: Sequence[str], num_biomarker: int,
