@@ -142,21 +142,28 @@ def build_scatter_plan(genes: torch.Tensor, offsets: torch.Tensor,
                        [int(x) for x in ptr])
 
 
+def _plan_slabs(plan: ScatterPlan):
+    """(seg_start, seg_gene) per slab, ascending (one L2-resident dO slice at
+    a time); an unslabbed plan is one slab, empty slabs are skipped."""
+    ptr = plan.slab_seg_ptr
+    if ptr is None:                 # whole tensors: no per-call slice views
+        if plan.seg_gene.numel():
+            yield plan.seg_start, plan.seg_gene
+        return
+    for a, b in zip(ptr[:-1], ptr[1:]):
+        if b > a:
+            yield plan.seg_start[a:b + 1], plan.seg_gene[a:b]
+
+
 def scatter_dO(genes, offsets, dO, n_genes: int,
                plan: Optional[ScatterPlan] = None):
     if dO.is_cuda:
         if plan is None:
             plan = build_scatter_plan(genes, offsets, n_genes)
-        if plan.slab_seg_ptr is None:
-            return native().scatter_dO_det(plan.inst_path, plan.seg_start,
-                                           plan.seg_gene, dO, int(n_genes))
         c = torch.zeros(n_genes, dtype=torch.float32, device=dO.device)
-        ptr = plan.slab_seg_ptr
-        for a, b in zip(ptr[:-1], ptr[1:]):     # ascending slabs: one
-            if b > a:                           # L2-resident slice at a time
-                native().scatter_dO_det_(plan.inst_path,
-                                         plan.seg_start[a:b + 1],
-                                         plan.seg_gene[a:b], dO, c)
+        for seg_start, seg_gene in _plan_slabs(plan):
+            native().scatter_dO_det_(plan.inst_path, seg_start, seg_gene,
+                                     dO, c)
         return c
     return cpu_ref.scatter_dO(genes, offsets, dO, n_genes)
 
@@ -328,22 +335,14 @@ def cbow_eval_counts_rep_(s_R, genes, offsets, labels, p_split: int,
 
 def scatter_dO_rep(plan: ScatterPlan, dO_R, n_genes: int) -> torch.Tensor:
     """Batched scatter_dO over the single trainer's ScatterPlan: c_R [G, R]
-    with c_R[:, r] = X^T dO_R[:, r]. Slab-blocked plans are driven slab by
-    slab in ascending order, as scatter_dO does (the slab size is the single
-    op's, not re-tuned for the R-times-larger table)."""
+    with c_R[:, r] = X^T dO_R[:, r], slab by slab like scatter_dO (the slab
+    size is the single op's, not re-tuned for the R-times-larger table)."""
     R = _rep_R(dO_R, "dO_R")
     c_R = torch.zeros(n_genes, R, dtype=torch.float32, device=dO_R.device)
     if dO_R.is_cuda:
-        if plan.slab_seg_ptr is None:
-            native().scatter_dO_rep_(plan.inst_path, plan.seg_start,
-                                     plan.seg_gene, dO_R, c_R)
-            return c_R
-        ptr = plan.slab_seg_ptr
-        for a, b in zip(ptr[:-1], ptr[1:]):
-            if b > a:
-                native().scatter_dO_rep_(plan.inst_path,
-                                         plan.seg_start[a:b + 1],
-                                         plan.seg_gene[a:b], dO_R, c_R)
+        for seg_start, seg_gene in _plan_slabs(plan):
+            native().scatter_dO_rep_(plan.inst_path, seg_start, seg_gene,
+                                     dO_R, c_R)
         return c_R
     # the plan lists each gene's instances in ascending path order, slab by
     # slab: the order cpu_ref.scatter_dO adds them in

@@ -6,6 +6,8 @@
 
 #include <climits>
 #include <cstdio>
+#include <functional>
+#include <initializer_list>
 #include <optional>
 #include <cstring>
 #include <fstream>
@@ -19,8 +21,8 @@
 namespace {
 
 // Every tensor a kernel dereferences passes one of these first: on the GPU,
-// contiguous, and (CHECK_F32 / CHECK_I32) of the dtype its data_ptr is
-// taken as. The message names the argument.
+// contiguous, and (CHECK_F32 / CHECK_I32 / CHECK_F64) of the dtype its
+// pointer is taken as. The message names the argument.
 inline void check_gpu_cont(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
@@ -33,9 +35,32 @@ inline void check_i32(const torch::Tensor& t, const char* name) {
   check_gpu_cont(t, name);
   TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
 }
+inline void check_f64(const torch::Tensor& t, const char* name) {
+  check_gpu_cont(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kDouble, name, " must be float64");
+}
+// the row-tile kernels move rows as 16-byte pieces
+inline void check_rows16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+}
 #define CHECK_GPU_CONT(x) check_gpu_cont((x), #x)
 #define CHECK_F32(x) check_f32((x), #x)
 #define CHECK_I32(x) check_i32((x), #x)
+#define CHECK_F64(x) check_f64((x), #x)
+#define CHECK_ROWS16(x) check_rows16((x), #x)
+
+// Every entry point with more than one tensor calls this directly after its
+// dtype checks: the launch goes to the current stream with raw pointers, so
+// a tensor of another GPU would be dereferenced on the wrong device.
+inline void check_same_device(
+    const torch::Tensor& first,
+    std::initializer_list<std::reference_wrapper<const torch::Tensor>> others) {
+  for (const torch::Tensor& t : others)
+    TORCH_CHECK(t.device() == first.device(),
+                "all tensors must be on one device, got ", first.device(),
+                " and ", t.device());
+}
 
 // A tensor size or user integer that a kernel receives as a 32-bit int goes
 // through here first: a value that does not fit is refused by name instead
@@ -46,21 +71,79 @@ inline int int_arg(long long v, const char* name) {
   return (int)v;
 }
 
+// The MFMA bodies are compiled only for gfx950: elsewhere the launch would be
+// a no-op leaving the outputs unwritten (the rank kernels are tuned and
+// tested for gfx950 alone and refuse other devices the same way).
+inline void check_gfx950(const char* op, const char* what = "MFMA kernel") {
+  hipDeviceProp_t prop;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipGetDeviceProperties(&prop, dev);
+  TORCH_CHECK(std::string(prop.gcnArchName).rfind("gfx950", 0) == 0, op,
+              ": ", what, " is gfx950-only, device reports ",
+              prop.gcnArchName);
+}
+
+inline int cu_count(const char* op) {
+  int n_cu = 0, dev = 0;
+  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
+                  hipDeviceGetAttribute(&n_cu,
+                                        hipDeviceAttributeMultiprocessorCount,
+                                        dev) == hipSuccess && n_cu >= 1,
+              op, ": cannot read the device's CU count");
+  return n_cu;
+}
+
+// the Adam kernels give each thread 4 columns of a row, whole rows per block
+inline void check_adam_hidden(int h) {
+  TORCH_CHECK(h >= 4 && h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
+              "hidden must be a multiple of 4 with h/4 dividing 256");
+}
+
 inline torch::TensorOptions opts_on(const torch::Tensor& t,
                                     at::ScalarType dtype = at::kFloat) {
   return torch::TensorOptions().dtype(dtype).device(t.device());
 }
 
+// The pointer a kernel receives; f32 of an absent optional is nullptr.
+inline float* f32(const torch::Tensor& t) { return t.data_ptr<float>(); }
+inline float* f32(const std::optional<torch::Tensor>& t) {
+  return t ? f32(*t) : nullptr;
+}
+inline int* i32(const torch::Tensor& t) { return t.data_ptr<int>(); }
+inline double* f64(const torch::Tensor& t) { return t.data_ptr<double>(); }
+inline uint8_t* u8(const torch::Tensor& t) { return t.data_ptr<uint8_t>(); }
+
 hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
 
-inline int grid_for(long long work_items, int per_block) {
+// THE launch: 256 threads on the current stream, each argument converted to
+// the kernel's parameter type, and the launch status read (LAUNCH_CHECK)
+// before anything else runs.
+template <typename... KA, typename... A>
+void launch(void (*k)(KA...), dim3 grid, size_t lds, A&&... a) {
+  static_assert(sizeof...(KA) == sizeof...(A), "kernel argument count");
+  hipLaunchKernelGGL(k, grid, dim3(256), lds, cur_stream(),
+                     static_cast<KA>(a)...);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "HIP launch failed: ",
+              hipGetErrorString(err));
+}
+
+// Blocks for work_items at per_block each: at least 1, at most cap, and never
+// past GRID_MAX (the kernels grid-stride over the rest).
+constexpr long long GRID_MAX = 1 << 20;
+inline int grid_for(long long work_items, int per_block,
+                    long long cap = GRID_MAX) {
   long long blocks = (work_items + per_block - 1) / per_block;
-  if (blocks > (1 << 20)) blocks = 1 << 20;
+  if (blocks > GRID_MAX) blocks = GRID_MAX;
+  if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
+// one row per wave (4 per block), at most the 8192 blocks that fill the chip
+inline int row_wave_grid(long long rows) { return grid_for(rows, 4, 8192); }
 
 // Integer env knob with a default, read on EVERY call (the tests flip the
 // knobs inside one process). Clamped to >= 1: a malformed value must not
@@ -70,13 +153,6 @@ inline int env_int_min1(const char* name, int dflt) {
   const int v = e ? atoi(e) : dflt;
   return v < 1 ? 1 : v;
 }
-
-#define LAUNCH_CHECK()                                                       \
-  do {                                                                       \
-    hipError_t err = hipGetLastError();                                      \
-    TORCH_CHECK(err == hipSuccess, "HIP launch failed: ",                    \
-                hipGetErrorString(err));                                     \
-  } while (0)
 
 // Template-parameter dispatch: f is a generic lambda called with a
 // std::integral_constant, so f's body names the kernel instantiation once.
@@ -114,6 +190,7 @@ std::vector<torch::Tensor> random_walks(torch::Tensor row_ptr, torch::Tensor col
                                         int64_t num_repetition, int64_t len_path,
                                         int64_t seed) {
   CHECK_I32(row_ptr); CHECK_I32(col_idx); CHECK_F32(weights); CHECK_I32(sources);
+  check_same_device(row_ptr, {col_idx, weights, sources});
   TORCH_CHECK(len_path >= 1 && len_path <= 512, "len_path out of range");
   const int n_src = int_arg(sources.numel(), "sources.numel()");
   const int num_rep = int_arg(num_repetition, "num_repetition");
@@ -126,48 +203,51 @@ std::vector<torch::Tensor> random_walks(torch::Tensor row_ptr, torch::Tensor col
   while (tsize < 2 * (int)len_path) tsize <<= 1;
   const int wpb = 4;                 // 256 threads = 4 waves
   const size_t lds = (size_t)wpb * (len_path + tsize) * sizeof(int);
-  hipLaunchKernelGGL(walk_kernel, dim3(grid_for(n_walks, wpb)), dim3(256), lds,
-                     cur_stream(), row_ptr.data_ptr<int>(),
-                     col_idx.data_ptr<int>(), weights.data_ptr<float>(),
-                     sources.data_ptr<int>(),
-                     n_src, n_walks, num_rep, (int)len_path,
-                     tsize, (uint64_t)seed,
-                     nodes.data_ptr<int>(), lengths.data_ptr<int>(),
-                     (long long*)hashes.data_ptr<int64_t>());
-  LAUNCH_CHECK();
+  launch(walk_kernel, grid_for(n_walks, wpb), lds, i32(row_ptr), i32(col_idx),
+         f32(weights), i32(sources), n_src, n_walks, num_rep, len_path, tsize,
+         seed, i32(nodes), i32(lengths),
+         (long long*)hashes.data_ptr<int64_t>());
   return {nodes, lengths, hashes};
 }
 
 // ------------------------------------------------------------ CBOW (fast)
+// offs is the CSR row pointer of the P paths: the kernels read offs[p + 1]
+inline void check_offs(const torch::Tensor& offs, long long P) {
+  TORCH_CHECK(offs.numel() == P + 1, "offs must have P + 1 elements");
+}
+inline void check_p_split(long long p_split, long long P) {
+  TORCH_CHECK(p_split >= 0 && p_split <= P, "p_split must be in [0, P]");
+}
+// seg_start is the CSR row pointer of the gene segments
+inline void check_seg_start(const torch::Tensor& seg_start, int n_seg) {
+  TORCH_CHECK(seg_start.numel() == (long long)n_seg + 1,
+              "seg_start must have n_seg + 1 elements");
+}
+
 std::vector<torch::Tensor> cbow_fwd_scalar(torch::Tensor s, torch::Tensor genes,
                                            torch::Tensor offs, torch::Tensor labels,
                                            double inv_b, bool want_grad) {
   CHECK_F32(s); CHECK_I32(genes); CHECK_I32(offs); CHECK_F32(labels);
+  check_same_device(s, {genes, offs, labels});
   const long long P = labels.numel();
+  check_offs(offs, P);
   auto loss = torch::empty({P}, opts_on(s));
   auto correct = torch::empty({P}, opts_on(s));
   auto dO = torch::empty({want_grad ? P : 0}, opts_on(s));
   if (P == 0) return {loss, correct, dO};
-  int grid = grid_for(P, 16);        // 16 paths per block (16-lane sub-waves)
-  if (grid > 2048) grid = 2048;      // dispatch ramp of 8k+ tiny blocks costs
-                                     // more than the grid-stride work itself
-  hipLaunchKernelGGL(cbow_fwd_scalar_kernel, dim3(grid), dim3(256),
-                     0, cur_stream(), s.data_ptr<float>(), genes.data_ptr<int>(),
-                     offs.data_ptr<int>(), labels.data_ptr<float>(), P,
-                     (float)inv_b, loss.data_ptr<float>(),
-                     correct.data_ptr<float>(),
-                     want_grad ? dO.data_ptr<float>() : nullptr);
-  LAUNCH_CHECK();
+  // 16 paths per block (16-lane sub-waves); capped because the dispatch ramp
+  // of 8k+ tiny blocks costs more than the grid-stride work itself
+  launch(cbow_fwd_scalar_kernel, grid_for(P, 16, 2048), 0, f32(s), i32(genes),
+         i32(offs), f32(labels), P, inv_b, f32(loss), f32(correct),
+         want_grad ? f32(dO) : nullptr);
   return {loss, correct, dO};
 }
 
 // second pass of every eval: one block folds the [grid, 2] per-block count
 // partials into counts[2]
 void fold_partials(const torch::Tensor& partials, torch::Tensor& counts) {
-  hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0,
-                     cur_stream(), partials.data_ptr<float>(),
-                     (int)partials.size(0), counts.data_ptr<float>());
-  LAUNCH_CHECK();
+  launch(fold_partials_kernel, 1, 0, f32(partials), partials.size(0),
+         f32(counts));
 }
 
 void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
@@ -181,8 +261,12 @@ void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
   }
   CHECK_F32(s); CHECK_I32(genes); CHECK_I32(offs); CHECK_F32(labels);
   CHECK_F32(counts);
+  check_same_device(s, {genes, offs, labels, counts});
+  if (dO) check_same_device(s, {*dO});
   TORCH_CHECK(counts.numel() == 2, "counts must have 2 elements");
   const long long P = labels.numel();
+  check_offs(offs, P);
+  check_p_split(p_split, P);
   if (P == 0) return;
   // LDS-staged variant (G2VEC_EVAL_LDS=<bytes> opts in when the whole s
   // table fits that per-block LDS budget): stages s in LDS so gathers are
@@ -197,28 +281,20 @@ void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
   const char* lds_env = getenv("G2VEC_EVAL_LDS");
   const long long lds_cap = lds_env ? atoll(lds_env) : 0;
   const bool lds = G * 4 <= lds_cap && G * 4 <= 158 * 1024;   // 160 KB LDS hard limit
-  int grid = grid_for(P, 16);       // 16 paths per block (16-lane sub-waves)
-  // G2VEC_EVAL_GRID: sweep knob; default 8192 waves fill the chip
-  const int gcap = lds ? env_int_min1("G2VEC_EVAL_LDS_GRID", 1024)
-                       : env_int_min1("G2VEC_EVAL_GRID", 2048);
-  if (grid > gcap) grid = gcap;
+  // 16 paths per block (16-lane sub-waves); G2VEC_EVAL_GRID: sweep knob,
+  // default 8192 waves fill the chip
+  const int grid =
+      grid_for(P, 16, lds ? env_int_min1("G2VEC_EVAL_LDS_GRID", 1024)
+                          : env_int_min1("G2VEC_EVAL_GRID", 2048));
   auto partials = torch::empty({grid, 2}, opts_on(s));
-  float* dOp = dO ? dO->data_ptr<float>() : nullptr;
   if (lds) {
-    hipLaunchKernelGGL(cbow_eval_counts_lds_kernel, dim3(grid),
-                       dim3(256), (size_t)(G * 4), cur_stream(),
-                       s.data_ptr<float>(),
-                       genes.data_ptr<int>(), offs.data_ptr<int>(),
-                       labels.data_ptr<float>(), P, (long long)p_split,
-                       partials.data_ptr<float>(), dOp, (float)inv_b, (int)G);
+    launch(cbow_eval_counts_lds_kernel, grid, G * 4, f32(s), i32(genes),
+           i32(offs), f32(labels), P, p_split, f32(partials), f32(dO), inv_b,
+           G);
   } else {
-    hipLaunchKernelGGL(cbow_eval_counts_kernel, dim3(grid),
-                       dim3(256), 0, cur_stream(), s.data_ptr<float>(),
-                       genes.data_ptr<int>(), offs.data_ptr<int>(),
-                       labels.data_ptr<float>(), P, (long long)p_split,
-                       partials.data_ptr<float>(), dOp, (float)inv_b);
+    launch(cbow_eval_counts_kernel, grid, 0, f32(s), i32(genes), i32(offs),
+           f32(labels), P, p_split, f32(partials), f32(dO), inv_b);
   }
-  LAUNCH_CHECK();
   fold_partials(partials, counts);
 }
 
@@ -231,39 +307,32 @@ void cbow_eval_scan_(torch::Tensor s, torch::Tensor genes,
   // persistent (hipGraph-stable) and sized P * cap
   CHECK_F32(s); CHECK_I32(genes); CHECK_I32(pathid); CHECK_I32(offs);
   CHECK_F32(labels); CHECK_F32(piece); CHECK_F32(counts);
+  check_same_device(s, {genes, pathid, offs, labels, piece, counts});
   const long long P = labels.numel();
   const long long nnz = genes.numel();
+  const int cap_i = int_arg(cap, "cap");
+  check_offs(offs, P);
+  check_p_split(p_split, P);
+  TORCH_CHECK(pathid.numel() == nnz,
+              "pathid must have one element per element of genes");
   TORCH_CHECK(piece.numel() >= P * cap, "piece buffer too small");
   if (dO) {
     CHECK_F32(*dO);
+    check_same_device(s, {*dO});
     TORCH_CHECK(dO->numel() >= p_split, "dO must cover the train split");
   }
   if (P == 0) return;
-  int grid_a = grid_for(nnz, 256);
+  // LDS-staged s (<= 48 KB tables): persistent blocks amortize the one-time
+  // stage, so the grid is capped
   const long long G = s.numel();
-  int g_lds = 0;
-  size_t lds = 0;
-  if (G * 4 <= 48 * 1024) {
-    // LDS-staged s: persistent blocks amortize the one-time 30 KB stage
-    g_lds = (int)G;
-    lds = (size_t)G * sizeof(float);
-    if (grid_a > 1536) grid_a = 1536;
-  }
-  hipLaunchKernelGGL(eval_scan_kernel, dim3(grid_a), dim3(256), lds,
-                     cur_stream(), s.data_ptr<float>(),
-                     genes.data_ptr<int>(), pathid.data_ptr<int>(),
-                     offs.data_ptr<int>(), nnz, (int)cap,
-                     piece.data_ptr<float>(), g_lds);
-  LAUNCH_CHECK();
-  int grid_b = grid_for(P, 256);
-  if (grid_b > 2048) grid_b = 2048;
+  const bool lds = G * 4 <= 48 * 1024;
+  launch(eval_scan_kernel, grid_for(nnz, 256, lds ? 1536 : GRID_MAX),
+         lds ? G * sizeof(float) : 0, f32(s), i32(genes), i32(pathid),
+         i32(offs), nnz, cap_i, f32(piece), lds ? G : 0);
+  const int grid_b = grid_for(P, 256, 2048);
   auto partials = torch::empty({grid_b, 2}, opts_on(s));
-  hipLaunchKernelGGL(eval_finish_kernel, dim3(grid_b), dim3(256), 0,
-                     cur_stream(), piece.data_ptr<float>(),
-                     offs.data_ptr<int>(), labels.data_ptr<float>(), P,
-                     (long long)p_split, (int)cap, partials.data_ptr<float>(),
-                     dO ? dO->data_ptr<float>() : nullptr, (float)inv_b);
-  LAUNCH_CHECK();
+  launch(eval_finish_kernel, grid_b, 0, f32(piece), i32(offs), f32(labels), P,
+         p_split, cap_i, f32(partials), f32(dO), inv_b);
   fold_partials(partials, counts);
 }
 
@@ -276,21 +345,12 @@ void scatter_dO_det_(torch::Tensor inst_path, torch::Tensor seg_start,
   // gathered instead of thrashing across the whole dO table.
   CHECK_I32(inst_path); CHECK_I32(seg_start); CHECK_I32(seg_gene);
   CHECK_F32(dO); CHECK_F32(c);
+  check_same_device(inst_path, {seg_start, seg_gene, dO, c});
   const int n_seg = int_arg(seg_gene.numel(), "seg_gene.numel()");
+  check_seg_start(seg_start, n_seg);
   if (n_seg == 0) return;
-  hipLaunchKernelGGL(scatter_do_det_kernel, dim3(grid_for(n_seg, 4)), dim3(256),
-                     0, cur_stream(), inst_path.data_ptr<int>(),
-                     seg_start.data_ptr<int>(), seg_gene.data_ptr<int>(),
-                     n_seg, dO.data_ptr<float>(), c.data_ptr<float>());
-  LAUNCH_CHECK();
-}
-
-torch::Tensor scatter_dO_det(torch::Tensor inst_path, torch::Tensor seg_start,
-                             torch::Tensor seg_gene, torch::Tensor dO,
-                             int64_t n_genes) {
-  auto c = torch::zeros({n_genes}, opts_on(dO));
-  scatter_dO_det_(inst_path, seg_start, seg_gene, dO, c);
-  return c;
+  launch(scatter_do_det_kernel, grid_for(n_seg, 4), 0, i32(inst_path),
+         i32(seg_start), i32(seg_gene), n_seg, f32(dO), f32(c));
 }
 
 // lr_t lives in a device slot (see adam_rank1_kernel); only element 0 is read
@@ -312,11 +372,11 @@ void adam_rank1(torch::Tensor W, torch::Tensor m, torch::Tensor v,
   // its extra full W read; deterministic block order).
   CHECK_F32(W); CHECK_F32(m); CHECK_F32(v); CHECK_F32(c); CHECK_F32(who);
   check_lrt(lrt);
+  check_same_device(W, {m, v, c, who, lrt});
   TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long G = W.size(0);
   const int h = int_arg(W.size(1), "W.size(1)");
-  TORCH_CHECK(h >= 4 && h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
-              "hidden must be a multiple of 4 with h/4 dividing 256");
+  check_adam_hidden(h);
   TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
               "m/v/W size mismatch");
   TORCH_CHECK(c.numel() == G, "c must have one element per W row");
@@ -324,31 +384,23 @@ void adam_rank1(torch::Tensor W, torch::Tensor m, torch::Tensor v,
   const int rpb = 256 / (h / 4);   // rows per 256-thread block
   const bool fused = mO.has_value();
   TORCH_CHECK(fused == vO.has_value(), "mO and vO go together");
-  int grid = grid_for(G, rpb);
+  // fused: the cap bounds the partial table / fold cost
+  const int grid = grid_for(G, rpb, fused ? 1024 : GRID_MAX);
   torch::Tensor partials;
   float* gw = nullptr;
   if (fused) {
     CHECK_F32(*mO); CHECK_F32(*vO);
+    check_same_device(W, {*mO, *vO});
     TORCH_CHECK(mO->numel() == h && vO->numel() == h,
                 "mO/vO must have one element per W column");
-    if (grid > 1024) grid = 1024;    // bound the partial table / fold cost
     partials = torch::empty({grid, h}, opts_on(W));
-    gw = partials.data_ptr<float>();
+    gw = f32(partials);
   }
-  hipLaunchKernelGGL(adam_rank1_kernel, dim3(grid), dim3(256), 0,
-                     cur_stream(), W.data_ptr<float>(), m.data_ptr<float>(),
-                     v.data_ptr<float>(), c.data_ptr<float>(),
-                     who.data_ptr<float>(), G, h, lrt.data_ptr<float>(),
-                     (float)b1, (float)b2, (float)eps, gw);
-  LAUNCH_CHECK();
-  if (fused) {
-    hipLaunchKernelGGL(fold_gw_adam_kernel, dim3(grid_for(h, 4)), dim3(256),
-                       0, cur_stream(), gw, grid, h, who.data_ptr<float>(),
-                       mO->data_ptr<float>(), vO->data_ptr<float>(),
-                       lrt.data_ptr<float>(), (float)b1, (float)b2,
-                       (float)eps);
-    LAUNCH_CHECK();
-  }
+  launch(adam_rank1_kernel, grid, 0, f32(W), f32(m), f32(v), f32(c), f32(who),
+         G, h, f32(lrt), b1, b2, eps, gw);
+  if (fused)
+    launch(fold_gw_adam_kernel, grid_for(h, 4), 0, gw, grid, h, f32(who),
+           f32(mO), f32(vO), f32(lrt), b1, b2, eps);
 }
 
 void adam_dense(torch::Tensor W, torch::Tensor m, torch::Tensor v,
@@ -356,15 +408,13 @@ void adam_dense(torch::Tensor W, torch::Tensor m, torch::Tensor v,
                 double eps) {
   CHECK_F32(W); CHECK_F32(m); CHECK_F32(v); CHECK_F32(grad);
   check_lrt(lrt);
+  check_same_device(W, {m, v, grad, lrt});
   TORCH_CHECK(grad.numel() == W.numel(), "grad/W size mismatch");
   TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
               "m/v/W size mismatch");
   const long long n = W.numel();
-  hipLaunchKernelGGL(adam_dense_kernel, dim3(grid_for(n, 256)), dim3(256), 0,
-                     cur_stream(), W.data_ptr<float>(), m.data_ptr<float>(),
-                     v.data_ptr<float>(), grad.data_ptr<float>(), n,
-                     lrt.data_ptr<float>(), (float)b1, (float)b2, (float)eps);
-  LAUNCH_CHECK();
+  launch(adam_dense_kernel, grid_for(n, 256), 0, f32(W), f32(m), f32(v),
+         f32(grad), n, f32(lrt), b1, b2, eps);
 }
 
 // ---------------------------------------------------------- CBOW (general)
@@ -378,10 +428,14 @@ std::vector<torch::Tensor> cbow_fwd(torch::Tensor W, torch::Tensor who,
   const bool fp16 = W.scalar_type() == at::kHalf;
   TORCH_CHECK(bf16 || fp16 || W.scalar_type() == at::kFloat,
               "W must be f32, bf16 or fp16");
+  check_same_device(W, {who, genes, offs, labels});
+  TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long P = labels.numel();
   const int h = int_arg(W.size(1), "W.size(1)");
   const int hpl = hpl_for(h);
   const int act_i = int_arg(act, "act");
+  TORCH_CHECK(who.numel() == h, "who must have one element per W column");
+  check_offs(offs, P);
   auto loss = torch::empty({P}, opts_on(W));
   auto correct = torch::empty({P}, opts_on(W));
   auto dO = torch::empty({want_grad ? P : 0}, opts_on(W));
@@ -389,25 +443,19 @@ std::vector<torch::Tensor> cbow_fwd(torch::Tensor W, torch::Tensor who,
                      : torch::empty({0}, opts_on(W));
   if (P == 0) return {loss, correct, dO, H};
   const int grid = grid_for(P, 4);
-  float* Hp = want_grad ? H.data_ptr<float>() : nullptr;
-  float* dOp = want_grad ? dO.data_ptr<float>() : nullptr;
   // Wp: the weight table as the kernel's element (tag) type
-  auto launch = [&](auto* Wp) {
+  auto go = [&](auto* Wp) {
     using WT = std::remove_cv_t<std::remove_pointer_t<decltype(Wp)>>;
     dispatch_hpl(hpl, [&](auto HPL) {
-      hipLaunchKernelGGL((cbow_fwd_kernel<WT, decltype(HPL)::value>),
-                         dim3(grid), dim3(256), 0, cur_stream(),
-                         (const WT*)Wp, who.data_ptr<float>(),
-                         genes.data_ptr<int>(), offs.data_ptr<int>(),
-                         labels.data_ptr<float>(), P, (float)inv_b, h, Hp,
-                         loss.data_ptr<float>(), correct.data_ptr<float>(),
-                         dOp, act_i);
-      LAUNCH_CHECK();
+      launch(cbow_fwd_kernel<WT, decltype(HPL)::value>, grid, 0, Wp, f32(who),
+             i32(genes), i32(offs), f32(labels), P, inv_b, h,
+             want_grad ? f32(H) : nullptr, f32(loss), f32(correct),
+             want_grad ? f32(dO) : nullptr, act_i);
     });
   };
-  if (bf16) launch((const bf16_bits*)W.data_ptr<at::BFloat16>());
-  else if (fp16) launch((const fp16_bits*)W.data_ptr<at::Half>());
-  else launch(W.data_ptr<float>());
+  if (bf16) go((const bf16_bits*)W.data_ptr<at::BFloat16>());
+  else if (fp16) go((const fp16_bits*)W.data_ptr<at::Half>());
+  else go(f32(W));
   return {loss, correct, dO, H};
 }
 
@@ -419,20 +467,18 @@ torch::Tensor cbow_bwd_rows(torch::Tensor who, torch::Tensor inst_path,
   CHECK_F32(who); CHECK_I32(inst_path); CHECK_I32(seg_start);
   CHECK_I32(seg_gene); CHECK_F32(dO);
   if (Hpre) CHECK_F32(*Hpre);
+  check_same_device(who, {inst_path, seg_start, seg_gene, dO});
+  if (Hpre) check_same_device(who, {*Hpre});
   const int h = int_arg(who.numel(), "who.numel()");
   const int hpl = hpl_for(h);
   const int n_seg = int_arg(seg_gene.numel(), "seg_gene.numel()");
+  check_seg_start(seg_start, n_seg);
   auto dW = torch::zeros({n_genes, h}, opts_on(dO));
   if (n_seg == 0) return dW;
-  const int grid = grid_for(n_seg, 4);
   dispatch_hpl(hpl, [&](auto HPL) {
-    hipLaunchKernelGGL((cbow_bwd_rows_det_kernel<decltype(HPL)::value>),
-                       dim3(grid), dim3(256), 0, cur_stream(),
-                       who.data_ptr<float>(), inst_path.data_ptr<int>(),
-                       seg_start.data_ptr<int>(), seg_gene.data_ptr<int>(),
-                       n_seg, dO.data_ptr<float>(), h, dW.data_ptr<float>(),
-                       Hpre ? Hpre->data_ptr<float>() : nullptr);
-    LAUNCH_CHECK();
+    launch(cbow_bwd_rows_det_kernel<decltype(HPL)::value>, grid_for(n_seg, 4),
+           0, f32(who), i32(inst_path), i32(seg_start), i32(seg_gene), n_seg,
+           f32(dO), h, f32(dW), f32(Hpre));
   });
   return dW;
 }
@@ -441,32 +487,24 @@ torch::Tensor cbow_bwd_rows(torch::Tensor who, torch::Tensor inst_path,
 torch::Tensor pcc_edges(torch::Tensor zt, torch::Tensor edge_idx,
                         int64_t n_group) {
   CHECK_F32(zt); CHECK_I32(edge_idx);
+  check_same_device(zt, {edge_idx});
+  TORCH_CHECK(zt.dim() == 2, "zt must be [G, S]");
+  TORCH_CHECK(edge_idx.dim() == 2 && edge_idx.size(1) == 2,
+              "edge_idx must be [E, 2]");
   const long long E = edge_idx.size(0);
   const int S = int_arg(zt.size(1), "zt.size(1)");
   auto out = torch::empty({E}, opts_on(zt));
   if (E == 0) return out;
-  hipLaunchKernelGGL(pcc_edges_kernel, dim3(grid_for(E, 4)), dim3(256), 0,
-                     cur_stream(), zt.data_ptr<float>(),
-                     edge_idx.data_ptr<int>(), E, S, 1.0f / (float)n_group,
-                     out.data_ptr<float>());
-  LAUNCH_CHECK();
+  launch(pcc_edges_kernel, grid_for(E, 4), 0, f32(zt), i32(edge_idx), E, S,
+         1.0f / (float)n_group, f32(out));
   return out;
 }
 
 torch::Tensor corr_gemm(torch::Tensor zt, int64_t n_group) {
   CHECK_F32(zt);
-  // the kernel body is compiled only for gfx950 (MFMA builtins): on any
-  // other arch the launch would be a no-op returning uninitialized C —
+  TORCH_CHECK(zt.dim() == 2, "zt must be [G, S]");
   // trap here instead of silently emitting garbage PCC weights
-  {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipGetDeviceProperties(&prop, dev);
-    TORCH_CHECK(std::string(prop.gcnArchName).rfind("gfx950", 0) == 0,
-                "corr_gemm: MFMA kernel is gfx950-only, device reports ",
-                prop.gcnArchName, " (use pcc_mode=edge)");
-  }
+  check_gfx950("corr_gemm", "MFMA kernel (use pcc_mode=edge)");
   const int G = int_arg(zt.size(0), "zt.size(0)");
   const int S = int_arg(zt.size(1), "zt.size(1)");
   // one block per 64 x 64 tile of C: the tile count is the launch's grid.x
@@ -480,11 +518,8 @@ torch::Tensor corr_gemm(torch::Tensor zt, int64_t n_group) {
   TORCH_CHECK(lds <= 160 * 1024,
               "corr_gemm: S too large for the LDS-staged tile (use pcc_mode=edge)");
   auto C = torch::empty({G, G}, opts_on(zt));
-  hipLaunchKernelGGL(corr_gemm_kernel, dim3((unsigned)(ntile * ntile)),
-                     dim3(256), lds,
-                     cur_stream(), zt.data_ptr<float>(), C.data_ptr<float>(),
-                     G, S, S4, 1.0f / (float)n_group);
-  LAUNCH_CHECK();
+  launch(corr_gemm_kernel, (unsigned)(ntile * ntile), lds, f32(zt), f32(C), G,
+         S, S4, 1.0f / (float)n_group);
   return C;
 }
 
@@ -492,30 +527,27 @@ void trunc_normal_(torch::Tensor out, double std, int64_t seed) {
   CHECK_F32(out);
   const long long n = (long long)out.numel();
   if (n == 0) return;
-  hipLaunchKernelGGL(trunc_normal_kernel, dim3(grid_for(n, 256)), dim3(256),
-                     0, cur_stream(), out.data_ptr<float>(), n, (float)std,
-                     (uint64_t)seed);
-  LAUNCH_CHECK();
+  launch(trunc_normal_kernel, grid_for(n, 256), 0, f32(out), n, std, seed);
 }
 
 void gemv_rows_(torch::Tensor W, torch::Tensor x, torch::Tensor out) {
   CHECK_F32(W); CHECK_F32(x); CHECK_F32(out);
+  check_same_device(W, {x, out});
+  TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long G = W.size(0);
   const int h = int_arg(W.size(1), "W.size(1)");
   const int hpl = hpl_for(h);
   TORCH_CHECK(out.numel() == G && x.numel() == h, "gemv_rows shape mismatch");
-  int grid = grid_for(G, 4);
-  if (grid > 8192) grid = 8192;
   dispatch_hpl(hpl, [&](auto HPL) {
-    hipLaunchKernelGGL((gemv_rows_kernel<decltype(HPL)::value>), dim3(grid),
-                       dim3(256), 0, cur_stream(), W.data_ptr<float>(),
-                       x.data_ptr<float>(), G, h, out.data_ptr<float>());
-    LAUNCH_CHECK();
+    launch(gemv_rows_kernel<decltype(HPL)::value>, row_wave_grid(G), 0, f32(W),
+           f32(x), G, h, f32(out));
   });
 }
 
 void gemv_cols_(torch::Tensor W, torch::Tensor c, torch::Tensor out) {
   CHECK_F32(W); CHECK_F32(c); CHECK_F32(out);
+  check_same_device(W, {c, out});
+  TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long G = W.size(0);
   const int h = int_arg(W.size(1), "W.size(1)");
   const int cpt = (h >= 256) ? h / 256 : 1;
@@ -524,18 +556,13 @@ void gemv_cols_(torch::Tensor W, torch::Tensor c, torch::Tensor out) {
   TORCH_CHECK(out.numel() == h && c.numel() == G, "gemv_cols shape mismatch");
   // ~8 rows per block: small G must still spread over the chip (8 blocks
   // for G=7.5k measured 78 us of serial row-walking; 941 blocks ~10 us)
-  const int grid = grid_for(G, 8) > 2048 ? 2048 : grid_for(G, 8);
+  const int grid = grid_for(G, 8, 2048);
   auto partials = torch::empty({grid, h}, opts_on(W));
   dispatch_cpt(cpt, [&](auto CPT) {
-    hipLaunchKernelGGL((gemv_cols_kernel<decltype(CPT)::value>), dim3(grid),
-                       dim3(256), 0, cur_stream(), W.data_ptr<float>(),
-                       c.data_ptr<float>(), G, h, partials.data_ptr<float>());
-    LAUNCH_CHECK();
+    launch(gemv_cols_kernel<decltype(CPT)::value>, grid, 0, f32(W), f32(c), G,
+           h, f32(partials));
   });
-  hipLaunchKernelGGL(fold_cols_kernel, dim3((h + 3) / 4), dim3(256), 0,
-                     cur_stream(), partials.data_ptr<float>(), grid, h,
-                     out.data_ptr<float>());
-  LAUNCH_CHECK();
+  launch(fold_cols_kernel, (h + 3) / 4, 0, f32(partials), grid, h, f32(out));
 }
 
 // --------------------------------------------- replica-batched fast path
@@ -579,36 +606,29 @@ void cbow_eval_counts_rep_(torch::Tensor s_R, torch::Tensor genes,
   // R] receives the train split's dlogits, rows >= p_split stay untouched
   const int R = check_rep_table(s_R, "s_R");
   CHECK_I32(genes); CHECK_I32(offs); CHECK_F32(labels); CHECK_F32(counts_R);
+  check_same_device(s_R, {genes, offs, labels, counts_R});
   TORCH_CHECK(counts_R.numel() == 2 * R, "counts_R must be [R, 2]");
   const long long P = labels.numel();
-  TORCH_CHECK(offs.numel() == P + 1, "offs must have P + 1 elements");
-  TORCH_CHECK(p_split >= 0 && p_split <= P, "p_split must be in [0, P]");
+  check_offs(offs, P);
+  check_p_split(p_split, P);
   if (dO_R) {
     CHECK_F32(*dO_R);
+    check_same_device(s_R, {*dO_R});
     TORCH_CHECK(dO_R->dim() == 2 && dO_R->size(1) == R &&
                     dO_R->size(0) >= p_split,
                 "dO_R must be [>= p_split, R]");
   }
   if (P == 0) return;
-  int grid = grid_for(P, 16);
-  const int gcap = env_int_min1("G2VEC_EVAL_GRID", 2048);
-  if (grid > gcap) grid = gcap;
+  const int grid = grid_for(P, 16, env_int_min1("G2VEC_EVAL_GRID", 2048));
   auto partials = torch::empty({grid, R, 2}, opts_on(s_R));
-  float* dOp = dO_R ? dO_R->data_ptr<float>() : nullptr;
-  dispatch_rep(R, s_R.data_ptr<float>(), [&](auto NT, auto VEC) {
-    hipLaunchKernelGGL(
-        (cbow_eval_counts_rep_kernel<decltype(NT)::value,
-                                     decltype(VEC)::value>),
-        dim3(grid), dim3(256), 0, cur_stream(), s_R.data_ptr<float>(),
-        genes.data_ptr<int>(), offs.data_ptr<int>(),
-        labels.data_ptr<float>(), P, (long long)p_split, R,
-        partials.data_ptr<float>(), dOp, (float)inv_b);
-    LAUNCH_CHECK();
+  dispatch_rep(R, f32(s_R), [&](auto NT, auto VEC) {
+    launch(cbow_eval_counts_rep_kernel<decltype(NT)::value,
+                                       decltype(VEC)::value>,
+           grid, 0, f32(s_R), i32(genes), i32(offs), f32(labels), P, p_split,
+           R, f32(partials), f32(dO_R), inv_b);
   });
-  hipLaunchKernelGGL(fold_partials_rep_kernel, dim3(R), dim3(256), 0,
-                     cur_stream(), partials.data_ptr<float>(), grid, R,
-                     counts_R.data_ptr<float>());
-  LAUNCH_CHECK();
+  launch(fold_partials_rep_kernel, R, 0, f32(partials), grid, R,
+         f32(counts_R));
 }
 
 void scatter_dO_rep_(torch::Tensor inst_path, torch::Tensor seg_start,
@@ -619,19 +639,15 @@ void scatter_dO_rep_(torch::Tensor inst_path, torch::Tensor seg_start,
   CHECK_I32(inst_path); CHECK_I32(seg_start); CHECK_I32(seg_gene);
   const int R = check_rep_table(dO_R, "dO_R");
   TORCH_CHECK(check_rep_table(c_R, "c_R") == R, "c_R and dO_R differ in R");
+  check_same_device(inst_path, {seg_start, seg_gene, dO_R, c_R});
   const int n_seg = int_arg(seg_gene.numel(), "seg_gene.numel()");
+  check_seg_start(seg_start, n_seg);
   if (n_seg == 0) return;
-  TORCH_CHECK(seg_start.numel() == (long long)n_seg + 1,
-              "seg_start must have n_seg + 1 elements");
   // dO_R decides VEC for both tables: c_R rows are written per lane
-  dispatch_rep(R, dO_R.data_ptr<float>(), [&](auto NT, auto VEC) {
-    hipLaunchKernelGGL(
-        (scatter_do_rep_kernel<decltype(NT)::value, decltype(VEC)::value>),
-        dim3(grid_for(n_seg, 4)), dim3(256), 0, cur_stream(),
-        inst_path.data_ptr<int>(), seg_start.data_ptr<int>(),
-        seg_gene.data_ptr<int>(), n_seg, dO_R.data_ptr<float>(), R,
-        c_R.data_ptr<float>());
-    LAUNCH_CHECK();
+  dispatch_rep(R, f32(dO_R), [&](auto NT, auto VEC) {
+    launch(scatter_do_rep_kernel<decltype(NT)::value, decltype(VEC)::value>,
+           grid_for(n_seg, 4), 0, i32(inst_path), i32(seg_start),
+           i32(seg_gene), n_seg, f32(dO_R), R, f32(c_R));
   });
 }
 
@@ -645,11 +661,11 @@ void adam_rank1_rep(torch::Tensor W, torch::Tensor m, torch::Tensor v,
   CHECK_F32(vO);
   check_lrt(lrt);
   const int R = check_rep_table(c_R, "c_R");
+  check_same_device(W, {m, v, c_R, who, mO, vO, lrt});
   TORCH_CHECK(W.dim() == 3 && W.size(0) == R, "W must be [R, G, h]");
   const long long G = W.size(1);
   const int h = int_arg(W.size(2), "W.size(2)");
-  TORCH_CHECK(h >= 4 && h % 4 == 0 && 256 % (h / 4) == 0 && h <= 1024,
-              "hidden must be a multiple of 4 with h/4 dividing 256");
+  check_adam_hidden(h);
   TORCH_CHECK(m.numel() == W.numel() && v.numel() == W.numel(),
               "m/v/W size mismatch");
   TORCH_CHECK(c_R.size(0) == G, "c_R must have one row per W row");
@@ -658,27 +674,18 @@ void adam_rank1_rep(torch::Tensor W, torch::Tensor m, torch::Tensor v,
               "who/mO/vO must be [R, h]");
   if (G == 0) return;
   const int rpb = 256 / (h / 4);
-  int grid = grid_for(G, rpb);
-  if (grid > 1024) grid = 1024;      // as the single fused launch
+  const int grid = grid_for(G, rpb, 1024);   // as the single fused launch
   auto partials = torch::empty({R, grid, h}, opts_on(W));
-  hipLaunchKernelGGL(adam_rank1_rep_kernel, dim3(grid, R), dim3(256), 0,
-                     cur_stream(), W.data_ptr<float>(), m.data_ptr<float>(),
-                     v.data_ptr<float>(), c_R.data_ptr<float>(),
-                     who.data_ptr<float>(), G, h, R, lrt.data_ptr<float>(),
-                     (float)b1, (float)b2, (float)eps,
-                     partials.data_ptr<float>());
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(fold_gw_adam_rep_kernel, dim3(grid_for(h, 4), R),
-                     dim3(256), 0, cur_stream(), partials.data_ptr<float>(),
-                     grid, h, who.data_ptr<float>(), mO.data_ptr<float>(),
-                     vO.data_ptr<float>(), lrt.data_ptr<float>(), (float)b1,
-                     (float)b2, (float)eps);
-  LAUNCH_CHECK();
+  launch(adam_rank1_rep_kernel, dim3(grid, R), 0, f32(W), f32(m), f32(v),
+         f32(c_R), f32(who), G, h, R, f32(lrt), b1, b2, eps, f32(partials));
+  launch(fold_gw_adam_rep_kernel, dim3(grid_for(h, 4), R), 0, f32(partials),
+         grid, h, f32(who), f32(mO), f32(vO), f32(lrt), b1, b2, eps);
 }
 
 void gemv_rows_rep_(torch::Tensor W, torch::Tensor who, torch::Tensor s_R) {
   CHECK_F32(W); CHECK_F32(who);
   const int R = check_rep_table(s_R, "s_R");
+  check_same_device(W, {who, s_R});
   TORCH_CHECK(W.dim() == 3 && W.size(0) == R, "W must be [R, G, h]");
   const long long G = W.size(1);
   const int h = int_arg(W.size(2), "W.size(2)");
@@ -686,14 +693,9 @@ void gemv_rows_rep_(torch::Tensor W, torch::Tensor who, torch::Tensor s_R) {
   TORCH_CHECK(s_R.size(0) == G && who.numel() == (long long)R * h,
               "gemv_rows_rep shape mismatch");
   if (G == 0) return;
-  int grid = grid_for(G, 4);
-  if (grid > 8192) grid = 8192;
   dispatch_hpl(hpl, [&](auto HPL) {
-    hipLaunchKernelGGL((gemv_rows_rep_kernel<decltype(HPL)::value>),
-                       dim3(grid, R), dim3(256), 0, cur_stream(),
-                       W.data_ptr<float>(), who.data_ptr<float>(), G, h, R,
-                       s_R.data_ptr<float>());
-    LAUNCH_CHECK();
+    launch(gemv_rows_rep_kernel<decltype(HPL)::value>,
+           dim3(row_wave_grid(G), R), 0, f32(W), f32(who), G, h, R, f32(s_R));
   });
 }
 
@@ -702,27 +704,12 @@ torch::Tensor bf16_copy(torch::Tensor src) {
   auto out = torch::empty_like(src, src.options().dtype(at::kBFloat16));
   const long long n = src.numel();
   if (n == 0) return out;
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n, 256)), dim3(256),
-                     0, cur_stream(), src.data_ptr<float>(),
-                     (uint16_t*)out.data_ptr<at::BFloat16>(), n);
-  LAUNCH_CHECK();
+  launch(f32_to_bf16_kernel, grid_for(n, 256), 0, f32(src),
+         (uint16_t*)out.data_ptr<at::BFloat16>(), n);
   return out;
 }
 
 // ------------------------------------------- steps 5-6: k-means and scoring
-inline void check_f64(const torch::Tensor& t, const char* name) {
-  check_gpu_cont(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kDouble, name, " must be float64");
-}
-#define CHECK_F64(x) check_f64((x), #x)
-
-// the row-tile kernels move rows as 16-byte pieces
-inline void check_rows16(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
-              " must be 16-byte aligned");
-}
-#define CHECK_ROWS16(x) check_rows16((x), #x)
-
 // kmeans_step LDS budget: k*h centroid floats + one [k][h] accumulator per
 // wave (4 waves) = 5*k*h floats of the CU's 160 KiB
 constexpr long long KM_LDS_LIMIT = 160 * 1024;
@@ -736,6 +723,8 @@ void kmeans_step(torch::Tensor X, torch::Tensor C, torch::Tensor prev,
   CHECK_F32(X); CHECK_F32(C); CHECK_I32(prev); CHECK_I32(labels);
   CHECK_F32(C_new); CHECK_F32(sums); CHECK_I32(counts); CHECK_I32(n_changed);
   CHECK_F64(inertia);
+  check_same_device(X, {C, prev, labels, C_new, sums, counts, n_changed,
+                        inertia});
   TORCH_CHECK(X.dim() == 2 && C.dim() == 2, "X must be [G, h] and C [k, h]");
   const long long G = X.size(0);
   const int h = int_arg(X.size(1), "X.size(1)");
@@ -762,39 +751,25 @@ void kmeans_step(torch::Tensor X, torch::Tensor C, torch::Tensor prev,
   // cap is what the chip holds at once (blocks per CU by LDS, at most the 8
   // that 32 waves allow): more blocks would queue behind the resident ones
   // and only lengthen the partial table ([grid, k*h]) and the fold
-  int n_cu = 0, dev = 0;
-  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
-                  hipDeviceGetAttribute(&n_cu,
-                                        hipDeviceAttributeMultiprocessorCount,
-                                        dev) == hipSuccess && n_cu >= 1,
-              "kmeans_step: cannot read the device's CU count");
   long long per_cu = KM_LDS_LIMIT / lds;
   if (per_cu > 8) per_cu = 8;
-  int grid = grid_for(G, 16);
-  if (grid > n_cu * per_cu) grid = (int)(n_cu * per_cu);
+  const int grid = grid_for(G, 16, cu_count("kmeans_step") * per_cu);
   auto psums = torch::empty({grid, k * h}, opts_on(X));
   auto pcnt = torch::empty({grid, KM_PCNT}, opts_on(X, at::kInt));
   auto pinert = torch::empty({grid}, opts_on(X, at::kDouble));
   dispatch_hpl(hpl, [&](auto HPL) {
-    hipLaunchKernelGGL((kmeans_step_kernel<decltype(HPL)::value>), dim3(grid),
-                       dim3(256), (size_t)lds, cur_stream(),
-                       X.data_ptr<float>(), C.data_ptr<float>(),
-                       prev.data_ptr<int>(), labels.data_ptr<int>(), G, h,
-                       (int)k, psums.data_ptr<float>(), pcnt.data_ptr<int>(),
-                       pinert.data_ptr<double>());
-    LAUNCH_CHECK();
+    launch(kmeans_step_kernel<decltype(HPL)::value>, grid, lds, f32(X), f32(C),
+           i32(prev), i32(labels), G, h, k, f32(psums), i32(pcnt),
+           f64(pinert));
   });
-  hipLaunchKernelGGL(kmeans_fold_kernel, dim3(grid_for(k * h, 4)), dim3(256),
-                     0, cur_stream(), psums.data_ptr<float>(),
-                     pcnt.data_ptr<int>(), pinert.data_ptr<double>(), grid,
-                     (int)k, h, C.data_ptr<float>(), C_new.data_ptr<float>(),
-                     sums.data_ptr<float>(), counts.data_ptr<int>(),
-                     n_changed.data_ptr<int>(), inertia.data_ptr<double>());
-  LAUNCH_CHECK();
+  launch(kmeans_fold_kernel, grid_for(k * h, 4), 0, f32(psums), i32(pcnt),
+         f64(pinert), grid, k, h, f32(C), f32(C_new), f32(sums), i32(counts),
+         i32(n_changed), f64(inertia));
 }
 
 void kmeans_mind2_(torch::Tensor X, torch::Tensor c, torch::Tensor d2) {
   CHECK_F32(X); CHECK_F32(c); CHECK_F32(d2);
+  check_same_device(X, {c, d2});
   TORCH_CHECK(X.dim() == 2, "X must be [G, h]");
   const long long G = X.size(0);
   const int h = int_arg(X.size(1), "X.size(1)");
@@ -803,19 +778,15 @@ void kmeans_mind2_(torch::Tensor X, torch::Tensor c, torch::Tensor d2) {
   TORCH_CHECK(d2.numel() == G, "d2 must have one element per X row");
   CHECK_ROWS16(X); CHECK_ROWS16(c);
   if (G == 0) return;
-  int grid = grid_for(G, 4);
-  if (grid > 8192) grid = 8192;
   dispatch_hpl(hpl, [&](auto HPL) {
-    hipLaunchKernelGGL((kmeans_mind2_kernel<decltype(HPL)::value>),
-                       dim3(grid), dim3(256), 0, cur_stream(),
-                       X.data_ptr<float>(), c.data_ptr<float>(), G, h,
-                       d2.data_ptr<float>());
-    LAUNCH_CHECK();
+    launch(kmeans_mind2_kernel<decltype(HPL)::value>, row_wave_grid(G), 0,
+           f32(X), f32(c), G, h, f32(d2));
   });
 }
 
 void row_norms_(torch::Tensor W, torch::Tensor out) {
   CHECK_F32(W); CHECK_F32(out);
+  check_same_device(W, {out});
   TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
   const long long G = W.size(0);
   const int h = int_arg(W.size(1), "W.size(1)");
@@ -823,13 +794,9 @@ void row_norms_(torch::Tensor W, torch::Tensor out) {
   TORCH_CHECK(out.numel() == G, "out must have one element per W row");
   CHECK_ROWS16(W);
   if (G == 0) return;
-  int grid = grid_for(G, 4);
-  if (grid > 8192) grid = 8192;
   dispatch_hpl(hpl, [&](auto HPL) {
-    hipLaunchKernelGGL((row_norms_kernel<decltype(HPL)::value>), dim3(grid),
-                       dim3(256), 0, cur_stream(), W.data_ptr<float>(), G, h,
-                       out.data_ptr<float>());
-    LAUNCH_CHECK();
+    launch(row_norms_kernel<decltype(HPL)::value>, row_wave_grid(G), 0, f32(W),
+           G, h, f32(out));
   });
 }
 
@@ -839,6 +806,7 @@ void t_scores_(torch::Tensor expr, torch::Tensor labels, torch::Tensor out) {
   TORCH_CHECK(labels.scalar_type() == at::kInt ||
                   labels.scalar_type() == at::kLong,
               "labels must be int32 or int64");
+  check_same_device(expr, {labels, out});
   TORCH_CHECK(expr.dim() == 2, "expr must be [S, G]");
   const long long S = expr.size(0);
   const long long G = expr.size(1);
@@ -847,28 +815,14 @@ void t_scores_(torch::Tensor expr, torch::Tensor labels, torch::Tensor out) {
   TORCH_CHECK(out.numel() == G, "out must have one element per gene");
   if (G == 0) return;
   auto lab = labels.to(at::kInt).contiguous();
-  hipLaunchKernelGGL(t_scores_kernel, dim3(grid_for(G, 256)), dim3(256), 0,
-                     cur_stream(), expr.data_ptr<float>(), lab.data_ptr<int>(),
-                     (int)S, G, out.data_ptr<float>());
-  LAUNCH_CHECK();
+  launch(t_scores_kernel, grid_for(G, 256), 0, f32(expr), i32(lab), S, G,
+         f32(out));
 }
 
 // ------------------------------------------- step 6: permutation null of t
-inline void check_gfx950(const char* op, const char* what = "MFMA kernel") {
-  // the MFMA body is compiled only for gfx950: elsewhere the launch would be
-  // a no-op leaving the outputs unwritten (the rank kernels are tuned and
-  // tested for gfx950 alone and refuse other devices the same way)
-  hipDeviceProp_t prop;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipGetDeviceProperties(&prop, dev);
-  TORCH_CHECK(std::string(prop.gcnArchName).rfind("gfx950", 0) == 0, op,
-              ": ", what, " is gfx950-only, device reports ",
-              prop.gcnArchName);
-}
-
 void col_moments_(torch::Tensor expr, torch::Tensor T, torch::Tensor Q) {
   CHECK_F32(expr); CHECK_F64(T); CHECK_F64(Q);
+  check_same_device(expr, {T, Q});
   TORCH_CHECK(expr.dim() == 2, "expr must be [S, G]");
   const long long S = expr.size(0);
   const long long G = expr.size(1);
@@ -877,10 +831,8 @@ void col_moments_(torch::Tensor expr, torch::Tensor T, torch::Tensor Q) {
                   Q.numel() == G,
               "T and Q must be [G]");
   if (G == 0) return;
-  hipLaunchKernelGGL(col_moments_kernel, dim3(grid_for(G, 256)), dim3(256), 0,
-                     cur_stream(), expr.data_ptr<float>(), (int)S, G,
-                     T.data_ptr<double>(), Q.data_ptr<double>());
-  LAUNCH_CHECK();
+  launch(col_moments_kernel, grid_for(G, 256), 0, f32(expr), S, G, f64(T),
+         f64(Q));
 }
 
 // shared guards of the two perm_t entry points; returns the launch grid
@@ -889,6 +841,7 @@ inline dim3 perm_t_check(const char* op, const torch::Tensor& expr,
                          const torch::Tensor& Q, int64_t n1) {
   CHECK_F32(expr); CHECK_GPU_CONT(masks); CHECK_F64(T); CHECK_F64(Q);
   TORCH_CHECK(masks.scalar_type() == at::kByte, "masks must be uint8");
+  check_same_device(expr, {masks, T, Q});
   TORCH_CHECK(expr.dim() == 2, "expr must be [S, G]");
   TORCH_CHECK(masks.dim() == 2, "masks must be [B, S]");
   const long long S = expr.size(0);
@@ -919,15 +872,13 @@ void perm_t_stats_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
                    torch::Tensor Q, int64_t n1, torch::Tensor out) {
   const dim3 grid = perm_t_check("perm_t_stats", expr, masks, T, Q, n1);
   CHECK_F64(out);
+  check_same_device(expr, {out});
   const long long S = expr.size(0), G = expr.size(1), B = masks.size(0);
   TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) == G,
               "out must be [B, G]");
   if (G == 0 || B == 0) return;
-  hipLaunchKernelGGL(perm_t_stats_kernel, grid, dim3(256), 0, cur_stream(),
-                     expr.data_ptr<float>(), masks.data_ptr<uint8_t>(),
-                     T.data_ptr<double>(), Q.data_ptr<double>(), (int)S, G, B,
-                     (int)n1, out.data_ptr<double>());
-  LAUNCH_CHECK();
+  launch(perm_t_stats_kernel, grid, 0, f32(expr), u8(masks), f64(T), f64(Q), S,
+         G, B, n1, f64(out));
 }
 
 void perm_t_counts_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
@@ -935,6 +886,7 @@ void perm_t_counts_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
                     torch::Tensor counts, torch::Tensor maxstat) {
   const dim3 grid = perm_t_check("perm_t_counts", expr, masks, T, Q, n1);
   CHECK_F64(stat_obs); CHECK_I32(counts); CHECK_F64(maxstat);
+  check_same_device(expr, {stat_obs, counts, maxstat});
   const long long S = expr.size(0), G = expr.size(1), B = masks.size(0);
   TORCH_CHECK(stat_obs.dim() == 1 && stat_obs.numel() == G,
               "stat_obs must be [G]");
@@ -943,19 +895,15 @@ void perm_t_counts_(torch::Tensor expr, torch::Tensor masks, torch::Tensor T,
               "maxstat must be [B]");
   // the kernel folds into both through integer atomics
   if (G > 0)
-    C10_HIP_CHECK(hipMemsetAsync(counts.data_ptr<int>(), 0, G * sizeof(int),
+    C10_HIP_CHECK(hipMemsetAsync(i32(counts), 0, G * sizeof(int),
                                  cur_stream()));
   if (B > 0)
-    C10_HIP_CHECK(hipMemsetAsync(maxstat.data_ptr<double>(), 0,
-                                 B * sizeof(double), cur_stream()));
+    C10_HIP_CHECK(hipMemsetAsync(f64(maxstat), 0, B * sizeof(double),
+                                 cur_stream()));
   if (G == 0 || B == 0) return;
-  hipLaunchKernelGGL(
-      perm_t_counts_kernel, grid, dim3(256), 0, cur_stream(),
-      expr.data_ptr<float>(), masks.data_ptr<uint8_t>(), T.data_ptr<double>(),
-      Q.data_ptr<double>(), stat_obs.data_ptr<double>(), (int)S, G, B, (int)n1,
-      counts.data_ptr<int>(),
-      reinterpret_cast<unsigned long long*>(maxstat.data_ptr<double>()));
-  LAUNCH_CHECK();
+  launch(perm_t_counts_kernel, grid, 0, f32(expr), u8(masks), f64(T), f64(Q),
+         f64(stat_obs), S, G, B, n1, i32(counts),
+         reinterpret_cast<unsigned long long*>(f64(maxstat)));
 }
 
 // ------------------------------------------- rank statistics
@@ -966,33 +914,25 @@ inline int rank_check(const char* op, const torch::Tensor& expr,
   CHECK_F32(expr);
   TORCH_CHECK(expr.dim() == 2, op, ": expr must be [S, G]");
   const long long S = expr.size(0);
-  const long long G = expr.size(1);
   // ranks are half-integers <= S: exact in f32 below 2^23
   TORCH_CHECK(S >= 1 && S < s_limit, op, " needs 1 <= S < ", s_limit,
               " samples, got ", S);
   int_arg(S, "expr.size(0)");
   check_gfx950(op, "rank kernel");
-  long long blocks = (G + RK_TG - 1) / RK_TG;
-  if (blocks > RK_MAX_BLOCKS) blocks = RK_MAX_BLOCKS;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
+  return grid_for(expr.size(1), RK_TG, RK_MAX_BLOCKS);
 }
 
 void rank_columns_(torch::Tensor expr, torch::Tensor ranks) {
   const int grid = rank_check("rank_columns", expr, 1LL << 23);
   CHECK_F32(ranks);
+  check_same_device(expr, {ranks});
   TORCH_CHECK(ranks.dim() == 2 && ranks.size(0) == expr.size(0) &&
                   ranks.size(1) == expr.size(1),
               "rank_columns: ranks must have expr's shape");
-  TORCH_CHECK(ranks.device() == expr.device(),
-              "rank_columns: expr and ranks must be on one device");
   const int S = int_arg(expr.size(0), "expr.size(0)");
   const long long G = expr.size(1);
   if (G == 0) return;
-  hipLaunchKernelGGL(rank_columns_kernel, dim3(grid), dim3(256), 0,
-                     cur_stream(), expr.data_ptr<float>(), S, G,
-                     ranks.data_ptr<float>());
-  LAUNCH_CHECK();
+  launch(rank_columns_kernel, grid, 0, f32(expr), S, G, f32(ranks));
 }
 
 void ranksum_scores_(torch::Tensor expr, torch::Tensor labels,
@@ -1000,6 +940,7 @@ void ranksum_scores_(torch::Tensor expr, torch::Tensor labels,
   // 4 SSR <= S^3 / 3 must fit the kernel's int64 sums
   const int grid = rank_check("ranksum_scores", expr, (1LL << 21) + 1);
   CHECK_I32(labels); CHECK_F32(z); CHECK_F32(auc);
+  check_same_device(expr, {labels, z, auc});
   const int S = int_arg(expr.size(0), "expr.size(0)");
   const long long G = expr.size(1);
   TORCH_CHECK(labels.dim() == 1 && labels.numel() == S,
@@ -1007,18 +948,12 @@ void ranksum_scores_(torch::Tensor expr, torch::Tensor labels,
   TORCH_CHECK(z.dim() == 1 && z.numel() == G && auc.dim() == 1 &&
                   auc.numel() == G,
               "ranksum_scores: z and auc must be [G]");
-  TORCH_CHECK(labels.device() == expr.device() &&
-                  z.device() == expr.device() && auc.device() == expr.device(),
-              "ranksum_scores: all tensors must be on one device");
   TORCH_CHECK(labels.min().item<int>() >= 0 && labels.max().item<int>() <= 1,
               "ranksum_scores: labels must hold only 0 and 1");
   const int n1 = int_arg(labels.sum().item<int64_t>(), "sum(labels)");
   if (G == 0) return;
-  hipLaunchKernelGGL(ranksum_scores_kernel, dim3(grid), dim3(256), 0,
-                     cur_stream(), expr.data_ptr<float>(),
-                     labels.data_ptr<int>(), S, G, n1, z.data_ptr<float>(),
-                     auc.data_ptr<float>());
-  LAUNCH_CHECK();
+  launch(ranksum_scores_kernel, grid, 0, f32(expr), i32(labels), S, G, n1,
+         f32(z), f32(auc));
 }
 
 // ------------------------------------------- nearest genes: MFMA GEMM + top-k
@@ -1038,17 +973,12 @@ int64_t knn_grid_y(int64_t Q, int64_t G, int64_t grid_y) {
   const long long nct = (G + KN_TILE - 1) / KN_TILE;
   long long gy = grid_y;
   if (gy == 0) {
-    int n_cu = 0, per_cu = 0, dev = 0;
-    TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
-                    hipDeviceGetAttribute(
-                        &n_cu, hipDeviceAttributeMultiprocessorCount, dev) ==
-                        hipSuccess &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                        &per_cu, knn_tile_kernel, 256, 0) == hipSuccess &&
-                    n_cu >= 1 && per_cu >= 1,
-                "knn_grid_y: cannot read the device's CU count and the "
-                "kernel's occupancy");
-    const long long resident = (long long)n_cu * per_cu;
+    int per_cu = 0;
+    TORCH_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &per_cu, knn_tile_kernel, 256, 0) == hipSuccess &&
+                    per_cu >= 1,
+                "knn_grid_y: cannot read the kernel's occupancy");
+    const long long resident = (long long)cu_count("knn_grid_y") * per_cu;
     gy = nqt > 0 ? (resident + nqt - 1) / nqt : 1;
   }
   if (gy > nct) gy = nct;
@@ -1065,6 +995,7 @@ void knn_topk_(torch::Tensor Xq, torch::Tensor X,
   // every guard runs before the first launch: a refused call leaves idx and
   // val as they were
   CHECK_F32(Xq); CHECK_F32(X); CHECK_I32(idx); CHECK_F32(val);
+  check_same_device(Xq, {X, idx, val});
   TORCH_CHECK(Xq.dim() == 2 && X.dim() == 2,
               "Xq must be [Q, h] and X [G, h]");
   const long long Q = Xq.size(0), G = X.size(0), h = X.size(1);
@@ -1074,15 +1005,11 @@ void knn_topk_(torch::Tensor Xq, torch::Tensor X,
   CHECK_ROWS16(Xq); CHECK_ROWS16(X);
   TORCH_CHECK(k >= 1 && k <= 64, "knn_topk: k must be in [1, 64], got ", k);
   TORCH_CHECK(G < (1LL << 31), "knn_topk: G must be below 2^31");
-  TORCH_CHECK(X.device() == Xq.device() && idx.device() == Xq.device() &&
-                  val.device() == Xq.device(),
-              "knn_topk: all tensors must be on one device");
   if (q_index) {
     CHECK_I32(*q_index);
+    check_same_device(Xq, {*q_index});
     TORCH_CHECK(q_index->dim() == 1 && q_index->numel() == Q,
                 "q_index must be [Q]");
-    TORCH_CHECK(q_index->device() == Xq.device(),
-                "knn_topk: all tensors must be on one device");
   }
   TORCH_CHECK(idx.dim() == 2 && idx.size(0) == Q && idx.size(1) == k &&
                   val.dim() == 2 && val.size(0) == Q && val.size(1) == k,
@@ -1096,29 +1023,20 @@ void knn_topk_(torch::Tensor Xq, torch::Tensor X,
                 "knn_topk: a split over ", gy,
                 " blocks needs the partial buffers");
     CHECK_I32(*part_idx); CHECK_F32(*part_val);
+    check_same_device(Xq, {*part_idx, *part_val});
     TORCH_CHECK(part_idx->numel() == Q * gy * k &&
                     part_val->numel() == Q * gy * k,
                 "part_idx and part_val must be [Q, ", gy, ", k]");
-    TORCH_CHECK(part_idx->device() == Xq.device() &&
-                    part_val->device() == Xq.device(),
-                "knn_topk: all tensors must be on one device");
   }
   check_gfx950("knn_topk");
   if (Q == 0) return;
-  const int* qi = q_index ? q_index->data_ptr<int>() : nullptr;
-  hipLaunchKernelGGL(
-      knn_tile_kernel, dim3((unsigned)nqt, (unsigned)gy), dim3(256), 0,
-      cur_stream(), Xq.data_ptr<float>(), X.data_ptr<float>(), qi, Q, G,
-      (int)h, (int)k, gy > 1 ? part_idx->data_ptr<int>() : idx.data_ptr<int>(),
-      gy > 1 ? part_val->data_ptr<float>() : val.data_ptr<float>());
-  LAUNCH_CHECK();
-  if (gy > 1) {
-    hipLaunchKernelGGL(knn_merge_kernel, dim3(grid_for(Q, 4)), dim3(256), 0,
-                       cur_stream(), part_idx->data_ptr<int>(),
-                       part_val->data_ptr<float>(), Q, (int)gy, (int)k,
-                       idx.data_ptr<int>(), val.data_ptr<float>());
-    LAUNCH_CHECK();
-  }
+  launch(knn_tile_kernel, dim3((unsigned)nqt, (unsigned)gy), 0, f32(Xq),
+         f32(X), q_index ? i32(*q_index) : nullptr, Q, G, h, k,
+         gy > 1 ? i32(*part_idx) : i32(idx),
+         gy > 1 ? f32(*part_val) : f32(val));
+  if (gy > 1)
+    launch(knn_merge_kernel, grid_for(Q, 4), 0, i32(*part_idx),
+           f32(*part_val), Q, gy, k, i32(idx), f32(val));
 }
 
 // ------------------------------------------------- native host TSV parser
@@ -1197,7 +1115,6 @@ parse_expression_tsv(const std::string& path) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("random_walks", &random_walks, "CSR biased random walks (gfx950)");
   m.def("cbow_fwd_scalar", &cbow_fwd_scalar, "scalar CBOW forward + loss");
-  m.def("scatter_dO_det", &scatter_dO_det, "deterministic c = X^T dO");
   m.def("scatter_dO_det_", &scatter_dO_det_,
         "deterministic c += X^T dO (one slab, out-arg)");
   m.def("cbow_eval_scan_", &cbow_eval_scan_,

@@ -566,3 +566,244 @@ def test_bf16_copy_crafted_bit_patterns():
     assert bool(torch.isnan(got.float()).all())
     sign = (got.view(torch.int16) < 0)
     assert torch.equal(sign, nan.view(torch.int32) < 0)   # sign kept
+
+
+# ======================================= argument guards of the older ops
+# A CSR pointer one short, a split outside [0, P] or a table of the wrong
+# rank used to reach the kernel and be indexed out of bounds. The smallest
+# real shapes: every refused call would run a handful of threads if let in.
+NG_P, NG_L, NG_G, NG_H, NG_S, NG_E = 4, 3, 8, 64, 8, 4
+NG_INV_B = 1.0 / NG_P
+
+
+def _ng_cpu():
+    gen = torch.Generator().manual_seed(91)
+    genes = torch.randint(0, NG_G, (NG_P * NG_L,), generator=gen).int()
+    offs = torch.arange(0, NG_P * NG_L + 1, NG_L, dtype=torch.int32)
+    plan = ops.build_scatter_plan(genes, offs, NG_G)
+    return dict(
+        genes=genes, offs=offs, labels=(torch.arange(NG_P) % 2).float(),
+        pathid=torch.repeat_interleave(
+            torch.arange(NG_P, dtype=torch.int32), NG_L),
+        s=ke.dyadic(gen, (NG_G,), 8), W=ke.dyadic(gen, (NG_G, NG_H), 8),
+        who=ke.dyadic(gen, (NG_H,), 8), cvec=ke.dyadic(gen, (NG_G,), 8),
+        dOin=torch.randint(-8, 9, (NG_P,), generator=gen).float(),
+        inst_path=plan.inst_path, seg_start=plan.seg_start,
+        seg_gene=plan.seg_gene,
+        zt=ke.int_rows(NG_G, NG_S, seed=92),
+        edge_idx=torch.randint(0, NG_G, (NG_E, 2), generator=gen).int())
+
+
+def _ng_inputs():
+    """The good arguments on the GPU plus sentinel-filled outputs (dO two
+    longer than P, so p_split = P + 1 meets the p_split guard first)."""
+    t = {k: v.to(DEV) for k, v in _ng_cpu().items()}
+    t.update(p_split=2, cap=2)
+    for name, shape in (("counts", 2), ("dO", NG_P + 2), ("c", NG_G),
+                        ("piece", NG_P * 2), ("out_rows", NG_G),
+                        ("out_cols", NG_H)):
+        t[name] = torch.full((shape,), -7.0, device=DEV)
+    return t
+
+
+NG_OPS = {
+    "fwd_scalar": lambda n, t: n.cbow_fwd_scalar(
+        t["s"], t["genes"], t["offs"], t["labels"], NG_INV_B, True),
+    "eval_counts": lambda n, t: n.cbow_eval_counts_(
+        t["s"], t["genes"], t["offs"], t["labels"], t["p_split"],
+        t["counts"], dO=t["dO"], inv_b=NG_INV_B),
+    "eval_scan": lambda n, t: n.cbow_eval_scan_(
+        t["s"], t["genes"], t["pathid"], t["offs"], t["labels"],
+        t["p_split"], t["cap"], t["piece"], t["counts"], dO=t["dO"],
+        inv_b=NG_INV_B),
+    "scatter": lambda n, t: n.scatter_dO_det_(
+        t["inst_path"], t["seg_start"], t["seg_gene"], t["dOin"], t["c"]),
+    "bwd_rows": lambda n, t: n.cbow_bwd_rows(
+        t["who"], t["inst_path"], t["seg_start"], t["seg_gene"], t["dOin"],
+        NG_G),
+    "cbow_fwd": lambda n, t: n.cbow_fwd(
+        t["W"], t["who"], t["genes"], t["offs"], t["labels"], NG_INV_B, True),
+    "gemv_rows": lambda n, t: n.gemv_rows_(t["W"], t["who"], t["out_rows"]),
+    "gemv_cols": lambda n, t: n.gemv_cols_(t["W"], t["cvec"], t["out_cols"]),
+    "pcc_edges": lambda n, t: n.pcc_edges(t["zt"], t["edge_idx"], N_GROUP),
+    "corr_gemm": lambda n, t: n.corr_gemm(t["zt"], N_GROUP),
+}
+
+
+def _short(name):
+    return lambda t: t.update({name: t[name][:-1].contiguous()})
+
+
+def _long(name):
+    return lambda t: t.update({name: torch.cat([t[name], t[name][-1:]])})
+
+
+def _set(name, value):
+    return lambda t: t.update({name: value})
+
+
+def _reshaped(name, *shape):
+    return lambda t: t.update({name: t[name].reshape(*shape)})
+
+
+_W_1D = _reshaped("W", -1)
+_W_3D = _reshaped("W", 2, NG_G // 2, NG_H)
+
+# case -> (op, what to break, the guard's message)
+NG_BAD_ARGS = {
+    **{f"{op}_offs_{kind}": (op, f("offs"), "offs must have")
+       for op in ("fwd_scalar", "eval_counts", "eval_scan", "cbow_fwd")
+       for kind, f in (("short", _short), ("long", _long))},
+    **{f"{op}_p_split_{name}": (op, _set("p_split", v), "p_split must be")
+       for op in ("eval_counts", "eval_scan")
+       for name, v in (("minus_1", -1), ("P_plus_1", NG_P + 1))},
+    "eval_scan_pathid_short": ("eval_scan", _short("pathid"),
+                               "pathid must have"),
+    "scatter_seg_start_short": ("scatter", _short("seg_start"),
+                                "seg_start must have"),
+    "bwd_rows_seg_start_short": ("bwd_rows", _short("seg_start"),
+                                 "seg_start must have"),
+    **{f"{op}_W_{name}": (op, f, r"W must be \[G, h\]")
+       for op in ("cbow_fwd", "gemv_rows", "gemv_cols")
+       for name, f in (("1d", _W_1D), ("3d", _W_3D))},
+    "cbow_fwd_who_128": ("cbow_fwd",
+                         lambda t: t.update(who=_bigger(t["who"], 2 * NG_H)),
+                         "who must have"),
+    "pcc_edges_edge_idx_Ex3": (
+        "pcc_edges",
+        lambda t: t.update(edge_idx=_bigger(t["edge_idx"], (NG_E, 3))),
+        "edge_idx must be"),
+    "pcc_edges_edge_idx_1d": ("pcc_edges", _reshaped("edge_idx", -1),
+                              "edge_idx must be"),
+    "pcc_edges_zt_1d": ("pcc_edges", _reshaped("zt", -1), "zt must be"),
+    "corr_gemm_zt_1d": ("corr_gemm", _reshaped("zt", -1), "zt must be"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(NG_BAD_ARGS))
+def test_older_bindings_reject_bad_arguments(case):
+    """Each case breaks one argument of one op: a RuntimeError from the host
+    that names the argument, with every tensor handed in (the sentinel-filled
+    outputs included) bitwise unchanged and nothing allocated."""
+    op, spoil, match = NG_BAD_ARGS[case]
+    t = _ng_inputs()
+    spoil(t)
+    tensors = {k: v for k, v in t.items() if isinstance(v, torch.Tensor)}
+    before = {k: v.clone() for k, v in tensors.items()}
+    torch.cuda.synchronize()
+    allocated = torch.cuda.memory_allocated()
+    with pytest.raises(RuntimeError, match=match):
+        NG_OPS[op](ops.native(), t)
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == allocated
+    for k, b in before.items():
+        assert torch.equal(tensors[k].view(torch.uint8),
+                           b.view(torch.uint8)), k
+
+
+def _ng_close(loss, correct, dO, ref):
+    """The scalar-forward bounds of this file: `correct` equal, loss 1e-5,
+    dO at the scaled project tolerance (exact sums, libm behind them)."""
+    rl, rc, rd = ref
+    assert torch.equal(correct.cpu(), rc)
+    assert _max_err(loss, rl.double()) <= 1e-5
+    assert _max_err(dO, rd.double()) <= ke.dO_tol(NG_INV_B)
+
+
+@pytest.mark.parametrize("op", sorted(NG_OPS))
+def test_older_bindings_accept_good_arguments(op):
+    """The same direct calls with the good arguments pass the guards and give
+    what cpu_ref gives: dyadic / integer inputs, so every sum is exact and
+    all but loss and dO (expf / log1pf) are compared bitwise."""
+    from g2vec_amd.ops import cpu_ref
+    c, t = _ng_cpu(), _ng_inputs()
+    t["counts"].zero_()          # the accumulating outputs start from zero
+    t["c"].zero_()
+    got = NG_OPS[op](ops.native(), t)
+    scalar = cpu_ref.cbow_fwd_scalar(c["s"], c["genes"], c["offs"],
+                                     c["labels"], NG_INV_B, True)
+    if op == "fwd_scalar":
+        _ng_close(*got, scalar)
+    elif op in ("eval_counts", "eval_scan"):
+        ps = t["p_split"]
+        assert t["counts"].tolist() == [float(scalar[1][:ps].sum()),
+                                        float(scalar[1][ps:].sum())]
+        assert _max_err(t["dO"][:ps], scalar[2][:ps].double()) \
+            <= ke.dO_tol(NG_INV_B)
+        assert bool((t["dO"][ps:] == -7.0).all())
+    elif op == "scatter":
+        assert torch.equal(t["c"].cpu(), cpu_ref.scatter_dO(
+            c["genes"], c["offs"], c["dOin"], NG_G))
+    elif op == "bwd_rows":
+        assert torch.equal(got.cpu(), cpu_ref.cbow_bwd_rows(
+            c["who"], c["genes"], c["offs"], c["dOin"], NG_G))
+    elif op == "cbow_fwd":
+        rl, rc, rd, rH = cpu_ref.cbow_fwd(c["W"], c["who"], c["genes"],
+                                          c["offs"], c["labels"], NG_INV_B,
+                                          True)
+        loss, correct, dO, H = got
+        assert torch.equal(H.cpu(), rH)
+        _ng_close(loss, correct, dO, (rl, rc, rd))
+    elif op == "gemv_rows":
+        assert torch.equal(t["out_rows"].cpu(), torch.mv(c["W"], c["who"]))
+    elif op == "gemv_cols":
+        assert torch.equal(t["out_cols"].cpu(),
+                           torch.mv(c["W"].t(), c["cvec"]))
+    elif op == "pcc_edges":
+        assert torch.equal(got.cpu(), cpu_ref.pcc_edges(
+            c["zt"], c["edge_idx"], N_GROUP))
+    else:
+        assert torch.equal(got.cpu(), cpu_ref.corr_gemm(c["zt"], N_GROUP))
+
+
+# one op per family, its second tensor moved to another GPU
+NG_OTHER_DEVICE = {
+    "walks": lambda n, a, b: n.random_walks(
+        a(torch.tensor([0, 1, 2], dtype=torch.int32)),
+        b(torch.tensor([1, 0], dtype=torch.int32)), a(torch.ones(2)),
+        a(torch.zeros(1, dtype=torch.int32)), 1, 2, 1),
+    "cbow_fast": lambda n, a, b: n.cbow_fwd_scalar(
+        a(torch.zeros(NG_G)), b(torch.zeros(3, dtype=torch.int32)),
+        a(torch.tensor([0, 3], dtype=torch.int32)), a(torch.zeros(1)),
+        1.0, False),
+    "adam": lambda n, a, b: n.adam_dense(
+        a(torch.zeros(4)), b(torch.zeros(4)), a(torch.zeros(4)),
+        a(torch.zeros(4)), a(torch.ones(1)), 0.9, 0.999, 1e-8),
+    "cbow_general": lambda n, a, b: n.cbow_fwd(
+        a(torch.zeros(NG_G, NG_H)), b(torch.zeros(NG_H)),
+        a(torch.zeros(3, dtype=torch.int32)),
+        a(torch.tensor([0, 3], dtype=torch.int32)), a(torch.zeros(1)),
+        1.0, False),
+    "gemv": lambda n, a, b: n.gemv_rows_(
+        a(torch.zeros(NG_G, NG_H)), b(torch.zeros(NG_H)),
+        a(torch.zeros(NG_G))),
+    "pcc": lambda n, a, b: n.pcc_edges(
+        a(torch.zeros(NG_G, NG_S)),
+        b(torch.zeros(NG_E, 2, dtype=torch.int32)), N_GROUP),
+    "replicas": lambda n, a, b: n.gemv_rows_rep_(
+        a(torch.zeros(2, NG_G, NG_H)), b(torch.zeros(2, NG_H)),
+        a(torch.zeros(NG_G, 2))),
+    "steps56": lambda n, a, b: n.row_norms_(
+        a(torch.zeros(NG_G, NG_H)), b(torch.zeros(NG_G))),
+    "perm": lambda n, a, b: n.col_moments_(
+        a(torch.zeros(NG_S, NG_G)),
+        b(torch.zeros(NG_G, dtype=torch.float64)),
+        a(torch.zeros(NG_G, dtype=torch.float64))),
+    "rank": lambda n, a, b: n.rank_columns_(
+        a(torch.zeros(NG_S, NG_G)), b(torch.zeros(NG_S, NG_G))),
+    "knn": lambda n, a, b: n.knn_topk_(
+        a(torch.zeros(2, NG_H)), b(torch.zeros(NG_G, NG_H)), None, 1, 1,
+        None, None, a(torch.zeros(2, 1, dtype=torch.int32)),
+        a(torch.zeros(2, 1))),
+}
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2,
+                    reason="needs a second GPU")
+@pytest.mark.parametrize("family", sorted(NG_OTHER_DEVICE))
+def test_bindings_refuse_tensors_of_two_devices(family):
+    """The launch hands raw pointers to the current stream: a tensor that
+    lives on cuda:1 next to one on cuda:0 is refused by the host."""
+    with pytest.raises(RuntimeError, match="must be on one device"):
+        NG_OTHER_DEVICE[family](ops.native(), lambda x: x.to("cuda:0"),
+                                lambda x: x.to("cuda:1"))
