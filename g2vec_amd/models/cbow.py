@@ -101,6 +101,10 @@ class TrainState:
     epoch_idx: int = 0
     # persistent fast-path buffers (stable addresses across hipGraph replays)
     s_buf: Optional[torch.Tensor] = None
+    c_buf: Optional[torch.Tensor] = None    # the GPU epoch body's c = X^T dO:
+                                            # all +0.0 at every epoch boundary
+                                            # (derived, so no snapshot or
+                                            # checkpoint carries it)
     lrt_buf: Optional[torch.Tensor] = None
     counts_buf: Optional[torch.Tensor] = None
     dO_buf: Optional[torch.Tensor] = None   # pending dlogits of the next step
@@ -110,6 +114,8 @@ class TrainState:
     graph: Any = None                # per-epoch hipGraph (_ensure_graph)
     graph_failed: bool = False
     kbufs: Optional[tuple] = None    # (klrt [K], kcounts [K, 2])
+    kparts: Optional[torch.Tensor] = None   # [K, eval grid, 2]: the block's
+                                            # count partials, folded once
     kgraph: Any = None               # K-epoch block graph (_ensure_kgraph)
     kblock_k: Optional[int] = None   # K of the recorded block graph
     kgraph_failed: bool = False
@@ -399,6 +405,8 @@ class CbowTrainer:
             st.s_buf = torch.empty(self.G, dtype=torch.float32,
                                    device=self.device)
             ops.gemv_rows(W, who, st.s_buf)
+            st.c_buf = torch.zeros(self.G, dtype=torch.float32,
+                                   device=self.device)
         st.lrt_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
         st.counts_buf = torch.zeros(2, dtype=torch.float32, device=self.device)
         # concatenated train+val evaluation set: both accuracy splits ride
@@ -422,7 +430,8 @@ class CbowTrainer:
         return st
 
     def _epoch_body_fast(self, st, counts_out=None, lrt_slot=None,
-                         reduce_counts: bool = True) -> None:
+                         reduce_counts: bool = True,
+                         partials_out=None) -> None:
         """One full-batch fast-path epoch as a capturable body: optimizer
         step at W_t, then post-update s + accuracy counts. All inputs and
         outputs live in persistent buffers (s_buf, lrt_buf, counts_buf) so
@@ -438,9 +447,20 @@ class CbowTrainer:
         (identical values — the sum over ranks commutes with the copy into
         the history). Steady-state collective cost: one grad all-reduce
         per epoch. Early-stop epochs keep reduce_counts=True (the stop
-        decision reads the global accuracy every epoch)."""
+        decision reads the global accuracy every epoch).
+
+        partials_out (block graph only): the eval parks its per-block
+        count partials in that table and folds nothing; counts_out is then
+        written by the block's ONE fold_partials_rows_ after its last body.
+
+        On GPU c lives in st.c_buf, zero on entry and zero again on exit:
+        the scatter accumulates into it, and the post-update GEMV — which
+        runs after Adam, c's only reader — clears it in the same launch, so
+        the chain has no fill node. Five kernels per epoch in a block
+        graph: scatter, adam_rank1, fold_gw_adam, gemv_rows, eval."""
         cfg = self.cfg
         tr, vl = st.tr, st.vl
+        on_gpu = self.device.type == "cuda"
         if counts_out is None:
             counts_out = st.counts_buf
         if self.device.type != "cuda" or st.ev_genes is None:
@@ -456,7 +476,7 @@ class CbowTrainer:
         # dO for THIS epoch's step was emitted by the previous epoch's
         # fused eval (or the setup() seeding) — no standalone forward
         c = ops.scatter_dO(tr.genes, tr.offsets, st.dO_buf, self.G,
-                           plan=st.plan)
+                           plan=st.plan, out=st.c_buf if on_gpu else None)
         self.ctx.allreduce_(c)                  # C1: whole dW_ih message
         # fused tail: one streaming pass over the pre-update W rows does
         # the rank-1 Adam AND emits dW_ho = W_pre^T c; a fold launch
@@ -468,11 +488,13 @@ class CbowTrainer:
         # fused eval kernel over the concatenated train+val paths, which
         # ALSO emits the next epoch's train dlogits (post-update s is the
         # next epoch's pre-update s — bitwise the same forward)
-        ops.gemv_rows(st.W, st.who, st.s_buf)
+        ops.gemv_rows(st.W, st.who, st.s_buf,
+                      clear=st.c_buf if on_gpu else None)
         if st.ev_genes is not None:
             ops.cbow_eval_counts_(st.s_buf, st.ev_genes, st.ev_offsets,
                                   st.ev_labels, tr.n_paths, counts_out,
-                                  dO=st.dO_buf, inv_b=st.inv_b)
+                                  dO=st.dO_buf, inv_b=st.inv_b,
+                                  partials=partials_out)
         if reduce_counts:
             self.ctx.allreduce_(counts_out)     # C3: 2-float metric reduce
 
@@ -601,7 +623,9 @@ class CbowTrainer:
         recorded body contains the grad all-reduce; capture is gated on
         the runtime RCCL-capture probe (see _ensure_graph). Bodies are
         recorded with reduce_counts=False — the kblocked runner all-
-        reduces the accuracy history once after the loop. When capture is
+        reduces the accuracy history once after the loop — and with their
+        count partials parked in st.kparts, folded by one launch recorded
+        after the K bodies (5K + 1 kernels per replay). When capture is
         unavailable the caller's eager tail loop runs every epoch — still
         with the deferred readback/reduce.
 
@@ -617,15 +641,30 @@ class CbowTrainer:
             st.kbufs = (
                 torch.empty(K, dtype=torch.float32, device=self.device),
                 torch.zeros(K, 2, dtype=torch.float32, device=self.device))
+            st.kparts = None
             st.kgraph = None
         if st.kgraph is None and not st.kgraph_failed:
             klrt, kcounts = st.kbufs
+            # body j parks its eval's count partials in row j of one table
+            # (<= 1 MB at K = 64) and ONE launch after the K bodies folds
+            # the rows into kcounts: nothing reads a block's counts before
+            # its replay has ended. A rank without paths runs no eval; its
+            # bodies zero their counts slots themselves.
+            if st.ev_genes is not None:
+                grid = ops.eval_grid(st.ev_labels.numel(), self.G)
+                if st.kparts is None or tuple(st.kparts.shape) != (K, grid, 2):
+                    st.kparts = torch.empty(K, grid, 2, dtype=torch.float32,
+                                            device=self.device)
+            kparts = st.kparts
 
             def bodies():
                 for j in range(K):
-                    self._epoch_body_fast(st, counts_out=kcounts[j],
-                                          lrt_slot=klrt[j:j + 1],
-                                          reduce_counts=False)
+                    self._epoch_body_fast(
+                        st, counts_out=kcounts[j], lrt_slot=klrt[j:j + 1],
+                        reduce_counts=False,
+                        partials_out=None if kparts is None else kparts[j])
+                if kparts is not None:
+                    ops.fold_partials_rows_(kparts, kcounts)
             # capture mutates no epoch state; on failure callers fall back
             # to the per-epoch path / eager tail loop
             st.kgraph = capture_graph(

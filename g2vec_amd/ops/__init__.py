@@ -56,9 +56,15 @@ def cbow_fwd_scalar(s, genes, offsets, labels, inv_b: float, want_grad: bool):
 
 def cbow_eval_counts_(s, genes, offsets, labels, p_split: int,
                       counts: torch.Tensor, dO: Optional[torch.Tensor] = None,
-                      inv_b: float = 1.0, scan=None) -> None:
+                      inv_b: float = 1.0, scan=None,
+                      partials: Optional[torch.Tensor] = None) -> None:
     """Accumulate the concatenated train+val correct counts into counts[2]
     (caller zeroes it). One fused kernel on GPU; oracle math on CPU.
+
+    partials (GPU, subwave eval only) = a caller-owned f32 [eval_grid(P, G),
+    2] table: the eval writes its per-block partials there, launches no
+    fold and leaves counts alone; fold_partials_rows_ folds a stack of such
+    tables later (the K-epoch block graph: one fold per block).
 
     dO given: also emit the train split's (p < p_split) dlogit into dO with
     scale inv_b — the fused next-epoch forward (this eval's s is the next
@@ -69,6 +75,8 @@ def cbow_eval_counts_(s, genes, offsets, labels, p_split: int,
     scan = (pathid i32[nnz], piece f32[>=P*cap], cap): persistent buffers
     enabling the instance-parallel segmented-scan variant — the hot
     steady-state eval (see eval_scan_kernel)."""
+    if partials is not None and (not s.is_cuda or scan is not None):
+        raise ValueError("partials goes with the GPU subwave eval only")
     if s.is_cuda:
         if scan is not None:
             pathid, piece, cap = scan
@@ -77,7 +85,8 @@ def cbow_eval_counts_(s, genes, offsets, labels, p_split: int,
                                      dO=dO, inv_b=float(inv_b))
             return
         native().cbow_eval_counts_(s, genes, offsets, labels, int(p_split),
-                                   counts, dO=dO, inv_b=float(inv_b))
+                                   counts, dO=dO, inv_b=float(inv_b),
+                                   partials=partials)
         return
     _l, corr, d = cpu_ref.cbow_fwd_scalar(s, genes, offsets, labels, inv_b,
                                           dO is not None)
@@ -85,6 +94,19 @@ def cbow_eval_counts_(s, genes, offsets, labels, p_split: int,
     counts[1] += corr[p_split:].sum()
     if dO is not None:
         dO.copy_(d[:p_split])
+
+
+def eval_grid(P: int, G: int) -> int:
+    """Rows of the per-block partial table the GPU eval of P paths over a
+    G-gene s table writes (G2VEC_EVAL_GRID / G2VEC_EVAL_LDS* applied, as
+    read at this call)."""
+    return int(native().eval_grid(int(P), int(G)))
+
+
+def fold_partials_rows_(partials: torch.Tensor, counts: torch.Tensor) -> None:
+    """counts [K, 2] (OVERWRITTEN) = the fold of K evals' partial tables
+    [K, grid, 2], each exactly as the eval's own fold would give it. GPU."""
+    native().fold_partials_rows_(partials, counts)
 
 
 class ScatterPlan(NamedTuple):
@@ -156,15 +178,26 @@ def _plan_slabs(plan: ScatterPlan):
 
 
 def scatter_dO(genes, offsets, dO, n_genes: int,
-               plan: Optional[ScatterPlan] = None):
+               plan: Optional[ScatterPlan] = None,
+               out: Optional[torch.Tensor] = None):
+    """c = X^T dO. out (GPU only) = a caller-owned f32 [n_genes] buffer that
+    is ALREADY all zero: the reduction accumulates into it and returns it,
+    with no allocation and no fill launch."""
     if dO.is_cuda:
         if plan is None:
             plan = build_scatter_plan(genes, offsets, n_genes)
-        c = torch.zeros(n_genes, dtype=torch.float32, device=dO.device)
+        if out is None:
+            c = torch.zeros(n_genes, dtype=torch.float32, device=dO.device)
+        else:
+            if out.numel() != n_genes:
+                raise ValueError("out must have n_genes elements")
+            c = out
         for seg_start, seg_gene in _plan_slabs(plan):
             native().scatter_dO_det_(plan.inst_path, seg_start, seg_gene,
                                      dO, c)
         return c
+    if out is not None:
+        raise ValueError("out goes with the GPU path only")
     return cpu_ref.scatter_dO(genes, offsets, dO, n_genes)
 
 
@@ -271,13 +304,16 @@ def cbow_bwd_rows(who, genes, offsets, dO, n_genes: int,
                                  H_pre=H_pre)
 
 
-def gemv_rows(W, x, out) -> None:
+def gemv_rows(W, x, out, clear: Optional[torch.Tensor] = None) -> None:
     """out = W @ x (tall-skinny GEMV). Own wave-per-row kernel on GPU:
-    rocBLAS gemvn ran at ~2% of HBM bandwidth on the [1M, 512] shape."""
+    rocBLAS gemvn ran at ~2% of HBM bandwidth on the [1M, 512] shape.
+    clear = an f32 [G] tensor zeroed (+0.0) by the same launch."""
     if W.is_cuda:
-        native().gemv_rows_(W, x, out)
+        native().gemv_rows_(W, x, out, clear=clear)
         return
     torch.mv(W, x, out=out)
+    if clear is not None:
+        clear.zero_()
 
 
 def gemv_cols(W, c, out) -> None:

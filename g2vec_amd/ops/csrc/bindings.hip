@@ -250,10 +250,57 @@ void fold_partials(const torch::Tensor& partials, torch::Tensor& counts) {
          f32(counts));
 }
 
+// fold_partials for K evals' tables at once: partials [K, grid, 2] ->
+// counts [K, 2], one block per table (the K-epoch block graph's one fold)
+void fold_partials_rows_(torch::Tensor partials, torch::Tensor counts) {
+  CHECK_F32(partials); CHECK_F32(counts);
+  check_same_device(partials, {counts});
+  TORCH_CHECK(partials.dim() == 3 && partials.size(2) == 2,
+              "partials must be [K, grid, 2]");
+  const int K = int_arg(partials.size(0), "partials.size(0)");
+  const int grid = int_arg(partials.size(1), "partials.size(1)");
+  TORCH_CHECK(counts.dim() == 2 && counts.size(0) == K && counts.size(1) == 2,
+              "counts must be [K, 2]");
+  if (K == 0) return;
+  launch(fold_partials_rows_kernel, K, 0, f32(partials), grid, f32(counts));
+}
+
+// The eval's launch geometry, in one place: the LDS-staged variant
+// (G2VEC_EVAL_LDS=<bytes> opts in when the whole s table fits that
+// per-block LDS budget) stages s in LDS so gathers are bank-parallel
+// ds_reads instead of L1 line-divergent loads, grid capped
+// (G2VEC_EVAL_LDS_GRID, default 1024) so each block amortizes its stage.
+// Bitwise-identical math. Measured (profiles/README.md, round 2): wins the
+// isolated microbench ~11% at ex_* shape (27.2 vs 30.2 us,
+// tools/bench_eval.py) but is NEUTRAL-to-slightly-worse inside the real
+// epoch chain (905 -> 893-902M paths/s same-box), so it is OFF by default —
+// kept as the documented measured alternative. Otherwise 16 paths per block
+// (16-lane sub-waves); G2VEC_EVAL_GRID: sweep knob, default 8192 waves fill
+// the chip. The knobs are read on every call.
+struct EvalGeom { bool lds; int grid; };
+inline EvalGeom eval_geom(long long P, long long G) {
+  const char* lds_env = getenv("G2VEC_EVAL_LDS");
+  const long long lds_cap = lds_env ? atoll(lds_env) : 0;
+  const bool lds = G * 4 <= lds_cap && G * 4 <= 158 * 1024;   // 160 KB LDS hard limit
+  return {lds, grid_for(P, 16, lds ? env_int_min1("G2VEC_EVAL_LDS_GRID", 1024)
+                                   : env_int_min1("G2VEC_EVAL_GRID", 2048))};
+}
+
+// rows of the per-block partial table an eval of P paths over a G-gene s
+// table writes: what a caller-owned `partials` of cbow_eval_counts_ must have
+int64_t eval_grid(int64_t P, int64_t G) {
+  TORCH_CHECK(P >= 0 && G >= 0, "eval_grid: P and G must be >= 0");
+  return eval_geom(P, G).grid;
+}
+
 void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
                        torch::Tensor labels, int64_t p_split,
                        torch::Tensor counts,
-                       std::optional<torch::Tensor> dO, double inv_b) {
+                       std::optional<torch::Tensor> dO, double inv_b,
+                       std::optional<torch::Tensor> partials_out) {
+  // partials_out [grid, 2] given: the per-block partials go there and NO
+  // fold is launched (counts is left as it is) — the caller folds a block of
+  // such tables with fold_partials_rows_
   if (dO) {
     CHECK_F32(*dO);
     TORCH_CHECK(dO->numel() >= p_split,
@@ -267,26 +314,18 @@ void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
   const long long P = labels.numel();
   check_offs(offs, P);
   check_p_split(p_split, P);
-  if (P == 0) return;
-  // LDS-staged variant (G2VEC_EVAL_LDS=<bytes> opts in when the whole s
-  // table fits that per-block LDS budget): stages s in LDS so gathers are
-  // bank-parallel ds_reads instead of L1 line-divergent loads, grid
-  // capped (G2VEC_EVAL_LDS_GRID, default 1024) so each block amortizes
-  // its stage. Bitwise-identical math. Measured (profiles/README.md,
-  // round 2): wins the isolated microbench ~11% at ex_* shape (27.2 vs
-  // 30.2 us, tools/bench_eval.py) but is NEUTRAL-to-slightly-worse
-  // inside the real epoch chain (905 -> 893-902M paths/s same-box), so
-  // it is OFF by default — kept as the documented measured alternative.
   const long long G = s.numel();
-  const char* lds_env = getenv("G2VEC_EVAL_LDS");
-  const long long lds_cap = lds_env ? atoll(lds_env) : 0;
-  const bool lds = G * 4 <= lds_cap && G * 4 <= 158 * 1024;   // 160 KB LDS hard limit
-  // 16 paths per block (16-lane sub-waves); G2VEC_EVAL_GRID: sweep knob,
-  // default 8192 waves fill the chip
-  const int grid =
-      grid_for(P, 16, lds ? env_int_min1("G2VEC_EVAL_LDS_GRID", 1024)
-                          : env_int_min1("G2VEC_EVAL_GRID", 2048));
-  auto partials = torch::empty({grid, 2}, opts_on(s));
+  const auto [lds, grid] = eval_geom(P, G);
+  if (partials_out) {
+    CHECK_F32(*partials_out);
+    check_same_device(s, {*partials_out});
+    TORCH_CHECK(partials_out->dim() == 2 && partials_out->size(0) == grid &&
+                    partials_out->size(1) == 2,
+                "partials must be [eval_grid(P, G), 2] = [", grid, ", 2]");
+  }
+  if (P == 0) return;
+  auto partials =
+      partials_out ? *partials_out : torch::empty({grid, 2}, opts_on(s));
   if (lds) {
     launch(cbow_eval_counts_lds_kernel, grid, G * 4, f32(s), i32(genes),
            i32(offs), f32(labels), P, p_split, f32(partials), f32(dO), inv_b,
@@ -295,7 +334,7 @@ void cbow_eval_counts_(torch::Tensor s, torch::Tensor genes, torch::Tensor offs,
     launch(cbow_eval_counts_kernel, grid, 0, f32(s), i32(genes), i32(offs),
            f32(labels), P, p_split, f32(partials), f32(dO), inv_b);
   }
-  fold_partials(partials, counts);
+  if (!partials_out) fold_partials(partials, counts);
 }
 
 void cbow_eval_scan_(torch::Tensor s, torch::Tensor genes,
@@ -530,7 +569,9 @@ void trunc_normal_(torch::Tensor out, double std, int64_t seed) {
   launch(trunc_normal_kernel, grid_for(n, 256), 0, f32(out), n, std, seed);
 }
 
-void gemv_rows_(torch::Tensor W, torch::Tensor x, torch::Tensor out) {
+void gemv_rows_(torch::Tensor W, torch::Tensor x, torch::Tensor out,
+                std::optional<torch::Tensor> clear) {
+  // clear [G] given: zeroed by the same launch (see gemv_rows_kernel)
   CHECK_F32(W); CHECK_F32(x); CHECK_F32(out);
   check_same_device(W, {x, out});
   TORCH_CHECK(W.dim() == 2, "W must be [G, h]");
@@ -538,9 +579,15 @@ void gemv_rows_(torch::Tensor W, torch::Tensor x, torch::Tensor out) {
   const int h = int_arg(W.size(1), "W.size(1)");
   const int hpl = hpl_for(h);
   TORCH_CHECK(out.numel() == G && x.numel() == h, "gemv_rows shape mismatch");
+  if (clear) {
+    CHECK_F32(*clear);
+    check_same_device(W, {*clear});
+    TORCH_CHECK(clear->numel() == G, "clear must have one element per W row");
+    TORCH_CHECK(clear->data_ptr() != out.data_ptr(), "clear must not be out");
+  }
   dispatch_hpl(hpl, [&](auto HPL) {
     launch(gemv_rows_kernel<decltype(HPL)::value>, row_wave_grid(G), 0, f32(W),
-           f32(x), G, h, f32(out));
+           f32(x), G, h, f32(out), f32(clear));
   });
 }
 
@@ -1127,7 +1174,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("s"), py::arg("genes"), py::arg("offs"), py::arg("labels"),
         py::arg("p_split"), py::arg("counts"),
         py::arg("dO") = py::none(), py::arg("inv_b") = 1.0,
-        "fused train/val correct-count eval (in-place counts[2])");
+        py::arg("partials") = py::none(),
+        "fused train/val correct-count eval (in-place counts[2]; partials "
+        "[eval_grid, 2] given: written instead, no fold)");
+  m.def("eval_grid", &eval_grid, py::arg("P"), py::arg("G"),
+        "block count of cbow_eval_counts_ = rows of its partial table");
+  m.def("fold_partials_rows_", &fold_partials_rows_, py::arg("partials"),
+        py::arg("counts"),
+        "counts [K, 2] = fold of K evals' partial tables [K, grid, 2]");
   m.def("adam_rank1", &adam_rank1,
         py::arg("W"), py::arg("m"), py::arg("v"), py::arg("c"),
         py::arg("who"), py::arg("lrt"), py::arg("b1"), py::arg("b2"),
@@ -1148,7 +1202,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("corr_gemm", &corr_gemm, "MFMA f32 correlation GEMM");
   m.def("trunc_normal_", &trunc_normal_,
         "seeded +-2sigma truncated-normal fill (K9)");
-  m.def("gemv_rows_", &gemv_rows_, "s = W @ x (wave-per-row GEMV, out-arg)");
+  m.def("gemv_rows_", &gemv_rows_, py::arg("W"), py::arg("x"), py::arg("out"),
+        py::arg("clear") = py::none(),
+        "s = W @ x (wave-per-row GEMV, out-arg; clear [G] given: zeroed too)");
   m.def("gemv_cols_", &gemv_cols_, "out = W^T c (partials + fold, out-arg)");
   m.def("cbow_eval_counts_rep_", &cbow_eval_counts_rep_,
         py::arg("s_R"), py::arg("genes"), py::arg("offs"), py::arg("labels"),

@@ -8,6 +8,7 @@
 //   cbow_eval_counts_kernel     fused eval: per-split correct counts + next-epoch train dlogits
 //   cbow_eval_counts_lds_kernel same body with the s table staged in LDS (opt-in)
 //   fold_partials_kernel        one-block fold of [n_blocks, 2] count partials
+//   fold_partials_rows_kernel   the same fold for K evals' partial tables, block per table
 //   cbow_eval_counts_rep_kernel<NT,VEC>  the eval body for R replicas (s_R [G, R]): one id load, R gathers
 //   fold_partials_rep_kernel    per-replica fold of its [n_blocks, R, 2] partials
 //   scatter_do_rep_kernel<NT,VEC>  c_R = X^T dO_R over the same plan, replica-minor
@@ -561,6 +562,22 @@ fold_partials_kernel(const float* __restrict__ partials, int n_blocks,
   block_fold2(c0, c1, counts);
 }
 
+// The same fold for a block of K evals at once: partials [K, n_blocks, 2],
+// counts [K, 2], block k folds row k exactly as fold_partials_kernel would.
+// The K-epoch block graph parks each epoch's partials in its own row and
+// folds them with this one launch instead of one per epoch.
+extern "C" __global__ void __launch_bounds__(256)
+fold_partials_rows_kernel(const float* __restrict__ partials, int n_blocks,
+                          float* __restrict__ counts) {
+  partials += (long long)blockIdx.x * n_blocks * 2;
+  float c0 = 0.f, c1 = 0.f;
+  for (int b = threadIdx.x; b < n_blocks; b += blockDim.x) {
+    c0 += partials[2 * b];
+    c1 += partials[2 * b + 1];
+  }
+  block_fold2(c0, c1, counts + 2 * blockIdx.x);
+}
+
 // ================================== replica-batched fast path (R <= REP_MAX)
 // R independently initialised models train on ONE path set: ids, offsets,
 // labels and the scatter plan are shared, the tables carry the replica
@@ -703,6 +720,34 @@ fold_partials_rep_kernel(const float* __restrict__ partials, int n_blocks,
 // =============================================== fast path: c = X^T dO (det.)
 // One wave per gene segment (instances pre-sorted by gene, plan built once
 // per path set). Fixed tree-reduction order -> bitwise reproducible.
+//
+// The order, per lane l of a segment [lo, hi) (scatter_do_rep_kernel spells
+// it as two loops): slot k is instance lo + l + 64k; group q = slots
+// 4q..4q+3 is FULL for the lane iff lo + l + 256q + 192 < hi; a full group
+// adds slot 4q+j into p_j, ascending q; every remaining slot goes into p0,
+// ascending, after the full groups; then wave_sum((p0 + p1) + (p2 + p3)).
+// A lane's full groups precede its other slots, so walking the slots once in
+// ascending order with the accumulator chosen per slot is that order.
+//
+// A segment is walked in ROUNDS of SCAT_U slots: SCAT_U id loads back to
+// back, SCAT_U gathers, then the adds in slot order, so a round costs two
+// memory round trips however many slots it has. SCAT_U is a multiple of 4,
+// so slot u of a round belongs to p_(u % 4) statically. A slot past hi
+// re-loads index hi - 1 (in range) and is dropped by a select, never by
+// adding 0.0f. The gene comes with the segment bounds and c[gene] is fetched
+// before the rounds. An empty segment runs no round.
+// Measured at the ex shape (profiles/README.md, "Epoch chain, second cut"):
+// the id loads are PLAIN loads — the 10 MB plan stays resident in the XCD
+// L2s from one epoch to the next, and nontemporal id loads cost 3 us per
+// launch (12.8 against 9.7 us); loading the next segment's bounds ahead,
+// as the eval does for paths, gained nothing, because the launch gives every
+// segment its own wave up to 4M segments, so the loop is a plain grid
+// stride.
+#ifndef SCAT_U
+#define SCAT_U 8
+#endif
+static_assert(SCAT_U >= 4 && SCAT_U % 4 == 0, "SCAT_U: whole groups of 4");
+
 extern "C" __global__ void __launch_bounds__(256)
 scatter_do_det_kernel(const int* __restrict__ inst_path,
                       const int* __restrict__ seg_start,
@@ -714,17 +759,35 @@ scatter_do_det_kernel(const int* __restrict__ inst_path,
   for (long long sidx = (long long)blockIdx.x * wpb + wib; sidx < n_seg;
        sidx += (long long)gridDim.x * wpb) {
     const int lo = seg_start[sidx], hi = seg_start[sidx + 1];
+    const int gene = seg_gene[sidx];
+    const float c_old = c[gene];
     float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-    int i = lo + lane;
-    for (; i + 3 * WAVE < hi; i += 4 * WAVE) {
-      p0 += dO[inst_path[i]];
-      p1 += dO[inst_path[i + WAVE]];
-      p2 += dO[inst_path[i + 2 * WAVE]];
-      p3 += dO[inst_path[i + 3 * WAVE]];
+    // rem = instances left from this lane's first slot of the round
+    // (<= 0: none); the round runs while its lane-0 slot is inside
+    int i0 = lo + lane;
+    for (int rem = hi - i0; rem + lane > 0;
+         rem -= SCAT_U * WAVE, i0 += SCAT_U * WAVE) {
+      int ip[SCAT_U];
+      float d[SCAT_U];
+#pragma unroll
+      for (int u = 0; u < SCAT_U; ++u)
+        ip[u] = inst_path[i0 + (u * WAVE < rem ? u * WAVE : rem - 1)];
+#pragma unroll
+      for (int u = 0; u < SCAT_U; ++u) d[u] = dO[ip[u]];
+#pragma unroll
+      for (int q = 0; q < SCAT_U / 4; ++q) {
+        const int k = 4 * q * WAVE;                // group's first slot offset
+        const bool full = k + 3 * WAVE < rem;
+        p0 = (k < rem) ? p0 + d[4 * q] : p0;
+        p1 = full ? p1 + d[4 * q + 1] : p1;
+        p0 = (!full && k + WAVE < rem) ? p0 + d[4 * q + 1] : p0;
+        p2 = full ? p2 + d[4 * q + 2] : p2;
+        p0 = (!full && k + 2 * WAVE < rem) ? p0 + d[4 * q + 2] : p0;
+        p3 = full ? p3 + d[4 * q + 3] : p3;
+      }
     }
-    for (; i < hi; i += WAVE) p0 += dO[inst_path[i]];
     const float v = wave_sum((p0 + p1) + (p2 + p3));
-    if (lane == 0) c[seg_gene[sidx]] += v;   // += so slab-blocked passes
+    if (lane == 0) c[gene] = c_old + v;      // += so slab-blocked passes
                                              // accumulate (c starts zeroed;
                                              // launches are stream-ordered,
                                              // so still deterministic)
@@ -869,6 +932,13 @@ adam_rank1_kernel(float* __restrict__ W, float* __restrict__ m,
 // in the same launch. One WAVE per column: lanes stride the block
 // partials (fixed stride + fixed shuffle tree -> deterministic); the
 // single-block variant was latency-bound at ~1k dependent loads/column.
+// Lane l sums rows l, l + 64, ... ascending (fold_gw_adam_rep_kernel spells
+// the plain loop); the strided row loads are issued FOLD_U at a time before
+// their adds — 16 covers the 1024-block cap of the fused launch in one
+// round — a slot past n_blocks re-loading the last row and dropped by a
+// select. mO/vO/who are fetched ahead of the fold.
+#define FOLD_U 16
+
 extern "C" __global__ void __launch_bounds__(256)
 fold_gw_adam_kernel(const float* __restrict__ partials, int n_blocks, int h,
                     float* __restrict__ who, float* __restrict__ mO,
@@ -880,16 +950,26 @@ fold_gw_adam_kernel(const float* __restrict__ partials, int n_blocks, int h,
   const int wib = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   for (int i = blockIdx.x * wpb + wib; i < h; i += gridDim.x * wpb) {
+    const float mO_i = mO[i], vO_i = vO[i], who_i = who[i];
     float g = 0.f;
-    for (int b = lane; b < n_blocks; b += WAVE)
-      g += partials[(long long)b * h + i];
+    for (int b0 = lane; b0 - lane < n_blocks; b0 += FOLD_U * WAVE) {
+      float pv[FOLD_U];
+#pragma unroll
+      for (int u = 0; u < FOLD_U; ++u) {
+        const int b = b0 + u * WAVE;
+        pv[u] = partials[(long long)(b < n_blocks ? b : n_blocks - 1) * h + i];
+      }
+#pragma unroll
+      for (int u = 0; u < FOLD_U; ++u)
+        g = (b0 + u * WAVE < n_blocks) ? g + pv[u] : g;
+    }
     g = wave_sum(g);
     if (lane == 0) {
-      const float mm = b1 * mO[i] + (1.f - b1) * g;
-      const float vv = b2 * vO[i] + (1.f - b2) * g * g;
+      const float mm = b1 * mO_i + (1.f - b1) * g;
+      const float vv = b2 * vO_i + (1.f - b2) * g * g;
       mO[i] = mm;
       vO[i] = vv;
-      who[i] -= lr_t * mm / (sqrtf(vv) + eps);
+      who[i] = who_i - lr_t * mm / (sqrtf(vv) + eps);
     }
   }
 }
@@ -1110,10 +1190,14 @@ corr_gemm_kernel(const float* __restrict__ zt, float* __restrict__ C,
 // rocBLAS gemvn on the tall-skinny [G, h] x [h] shape ran at ~2% of HBM
 // bandwidth (18.6 ms for the 1M x 512 s = W_ih @ W_ho). One wave per row,
 // h/64 contiguous columns per lane, wave-reduce: HBM-roofline instead.
+// clear != nullptr: the row's wave also stores clear[g] = 0.0f. The epoch
+// body passes its c buffer: this GEMV runs after Adam, the only reader of
+// c, and before the next scatter, so c is zero again without a fill node.
 template <int HPL>
 __global__ void __launch_bounds__(256)
 gemv_rows_kernel(const float* __restrict__ W, const float* __restrict__ x,
-                 long long G, int h, float* __restrict__ out) {
+                 long long G, int h, float* __restrict__ out,
+                 float* __restrict__ clear) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wib = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
@@ -1128,7 +1212,10 @@ gemv_rows_kernel(const float* __restrict__ W, const float* __restrict__ x,
 #pragma unroll
     for (int k = 0; k < HPL; ++k) p += acc[k] * xv[k];
     const float o = wave_sum(p);
-    if (lane == 0) out[g] = o;
+    if (lane == 0) {
+      out[g] = o;
+      if (clear) clear[g] = 0.0f;
+    }
   }
 }
 
