@@ -113,6 +113,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "Wilcoxon rank-sum |z| (the scores table then holds "
                         "z_ranksum and auc; --permutations gives the exact "
                         "permutation rank-sum p-values)")
+    p.add_argument("--silhouette", action="store_true",
+                   help="score the L-group split: per-gene silhouette over "
+                        "the embedding (exact Euclidean, all gene pairs) and "
+                        "the nearest other L-group, as the silhouette and "
+                        "nearest_lgroup columns of the scores table; implies "
+                        "--write-scores")
     p.add_argument("--save-paths", type=str, default="")
     p.add_argument("--load-model", type=str, default="",
                    help="skip training: load W_ih from a --save-model .pt "
@@ -145,10 +151,11 @@ def args_to_config(a: argparse.Namespace) -> G2VecConfig:
         load_model=a.load_model,
         log_jsonl=a.log_jsonl,
         use_hipgraph=not a.no_hipgraph,
-        write_scores=a.write_scores or a.permutations > 0,
+        write_scores=a.write_scores or a.permutations > 0 or a.silhouette,
         permutations=a.permutations, perm_seed=a.perm_seed,
         neighbors=a.neighbors, neighbors_of=a.neighbors_of,
-        replicates=a.replicates, corr=a.corr, score_stat=a.score_stat)
+        replicates=a.replicates, corr=a.corr, score_stat=a.score_stat,
+        silhouette=a.silhouette)
 
 
 def main(argv=None) -> int:

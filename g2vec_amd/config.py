@@ -123,6 +123,12 @@ class G2VecConfig:
                                     # carries z_ranksum and auc, and
                                     # --permutations runs on the ranks)
 
+    silhouette: bool = dataclasses.field(default=False, repr=False)
+                                    # also score the L-group split: per-gene
+                                    # silhouettes over the embedding
+                                    # (cluster_quality.py) as two columns of
+                                    # the scores table (implies write_scores)
+
     def check_replicate_scope(self) -> None:
         """The batched trainer covers the default training regime only; any
         other option is an error that names it, never a silent no-op."""
@@ -194,7 +200,7 @@ class G2VecConfig:
             raise ValueError("permutations must be >= 0 (0 = off)")
         if self.perm_seed is not None and self.perm_seed < 0:
             raise ValueError("perm_seed must be >= 0")
-        if self.permutations > 0:
+        if self.permutations > 0 or self.silhouette:
             self.write_scores = True
         if not 0 <= self.neighbors <= 64:
             raise ValueError("neighbors must be in [0, 64] (0 = off)")

@@ -68,12 +68,19 @@ def write_scores(result_name: str, genes: Sequence[str],
     outside L-groups 0 and 1), biomarker (0/1) and, with perm (the dict of
     scoring.permutation_pvalues), p_perm, q_bh, p_maxT. Scores are printed
     %.6f, p-values %.6g. When scores carries "auc" (the rank-sum statistic
-    was scored), the t_score column is named z_ranksum and auc follows it."""
+    was scored), the t_score column is named z_ranksum and auc follows it.
+    When scores carries "silhouette" (f64 [G], or None where the split has
+    fewer than two non-empty L-groups) with "nearest_lgroup", the columns
+    silhouette (%.6f) and nearest_lgroup (%d) follow biomarker; NA for
+    None."""
     out = result_name + "_scores.txt"
     ranksum = "auc" in scores
     cols = ["GeneSymbol", "Lgroup", "d_score"] + (
         ["z_ranksum", "auc"] if ranksum else ["t_score"]) + [
         "gene_score", "biomarker"]
+    sil = "silhouette" in scores
+    if sil:
+        cols += ["silhouette", "nearest_lgroup"]
     if perm is not None:
         cols += ["p_perm", "q_bh", "p_maxT"]
     gs = np.asarray(scores["gene_score"], dtype=np.float64)
@@ -86,6 +93,11 @@ def write_scores(result_name: str, genes: Sequence[str],
                    ["%.6f" % float(scores["auc"][i])] if ranksum else []) + [
                    "NA" if np.isnan(gs[i]) else "%.6f" % gs[i],
                    "%d" % int(scores["is_biomarker"][i])]
+            if sil and scores["silhouette"] is None:
+                row += ["NA", "NA"]
+            elif sil:
+                row += ["%.6f" % float(scores["silhouette"][i]),
+                        "%d" % int(scores["nearest_lgroup"][i])]
             if perm is not None:
                 row += ["%.6g" % float(perm[k][i])
                         for k in ("p", "q_bh", "p_maxT")]

@@ -695,3 +695,76 @@ def knn_topk(Xq, X, k: int, q_index=None, grid_y: int = 0):
     nat.knn_topk_(Xq, X, q_index, int(k), int(grid_y), part_idx, part_val,
                   idx, val)
     return idx, val
+
+
+# ------------------------------------------------------------------ L-group silhouettes
+CDS_K_MAX = 8           # clusters per call, the limit of kmeans_step
+
+
+def cluster_dist_sums(Xq, X, labels, k: int, q_index=None, grid_y: int = 0):
+    """D f64 [Q, k]: D[q, c] = the sum over the rows g of X f32 [G, h] with
+    labels[g] == c and g != q_index[q] of the Euclidean distance
+    d(q, g) = sqrtf(max(nq[q] + nx[g] - 2 dot(Xq[q], X[g]), 0)) to row q of
+    Xq f32 [Q, h]; nq / nx are the squared row norms (f64-accumulated,
+    rounded once), d is f32, the sums are f64. labels i32/i64 [G] in [0, k),
+    1 <= k <= 8; q_index i32/i64 [Q] (-1 or None excludes nothing); inputs
+    finite. An empty cluster's column is +0.0. Bitwise equal run to run for
+    a given grid_y (GPU launch split over the candidates; 0 = automatic);
+    across splits only the f64 addition order changes. Widths that are no
+    multiple of 4 are zero-padded (exact) on the GPU."""
+    for name, t in (("Xq", Xq), ("X", X)):
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError(f"{name} must be a float32 [rows, h] tensor")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if Xq.shape[1] != X.shape[1]:
+        raise ValueError(f"Xq has {Xq.shape[1]} columns, X has {X.shape[1]}")
+    if X.device != Xq.device:
+        raise ValueError("Xq and X must be on the same device")
+    if not 1 <= int(k) <= CDS_K_MAX:
+        raise ValueError(f"k must be in [1, {CDS_K_MAX}], got {k}")
+    k = int(k)
+    Q, G = Xq.shape[0], X.shape[0]
+    if G >= 2 ** 31:
+        raise ValueError("X must have fewer than 2^31 rows")
+    if grid_y < 0:
+        raise ValueError("grid_y must be >= 0")
+    if labels.dim() != 1 or labels.shape[0] != G or \
+            labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError("labels must be an int32/int64 [G] tensor")
+    if labels.device != X.device:
+        raise ValueError("labels must be on X's device")
+    bad = ((labels < 0) | (labels >= k)).nonzero()
+    if bad.numel():
+        g = int(bad[0])
+        raise ValueError(f"labels must lie in [0, {k}): labels[{g}] = "
+                         f"{int(labels[g])}")
+    if not (bool(torch.isfinite(Xq).all()) and bool(torch.isfinite(X).all())):
+        raise ValueError("Xq and X must be finite")
+    if q_index is not None:
+        if q_index.dim() != 1 or q_index.shape[0] != Q or \
+                q_index.dtype not in (torch.int32, torch.int64):
+            raise ValueError("q_index must be an int32/int64 [Q] tensor")
+        if q_index.device != Xq.device:
+            raise ValueError("q_index must be on Xq's device")
+        q_index = q_index.int().contiguous()
+    labels = labels.int().contiguous()
+    if not Xq.is_cuda:
+        return cpu_ref.cluster_dist_sums(Xq, X, labels, k, q_index)
+    nat = native()
+    pad = -X.shape[1] % 4
+    if pad or X.shape[1] == 0:
+        pad = pad or 4
+        Xq = torch.nn.functional.pad(Xq, (0, pad))
+        X = torch.nn.functional.pad(X, (0, pad))
+    dev = Xq.device
+    D = torch.empty(Q, k, dtype=torch.float64, device=dev)
+    nq = torch.empty(Q, dtype=torch.float32, device=dev)
+    nx = torch.empty(G, dtype=torch.float32, device=dev)
+    gy = nat.cds_grid_y(Q, G, k, int(grid_y))
+    part = None
+    if gy > 1:
+        part = torch.empty(Q, gy, k, dtype=torch.float64, device=dev)
+    nat.cluster_dist_sums_(Xq, X, labels, q_index, k, int(grid_y), nq, nx,
+                           part, D)
+    return D

@@ -524,3 +524,48 @@ def knn_topk(Xq: torch.Tensor, X: torch.Tensor, k: int,
         out_idx[q0:q0 + n] = idx[:n]
     out_idx[out_val == ninf] = -1
     return out_idx.int(), out_val
+
+
+# ------------------------------------------------------ L-group silhouettes
+def row_sqnorms(X: torch.Tensor) -> torch.Tensor:
+    """f32 [G]: squared row norms accumulated in f64, rounded to f32 once
+    (row_sqnorms_kernel)."""
+    Xd = X.double()
+    return (Xd * Xd).sum(dim=1).float()
+
+
+def cluster_dist_sums(Xq: torch.Tensor, X: torch.Tensor, labels: torch.Tensor,
+                      k: int, q_index=None) -> torch.Tensor:
+    """D f64 [Q, k] of cds_tile_kernel: D[q, c] = the sum over the rows g of
+    X with labels[g] == c and g != q_index[q] of the f32 distance
+    sqrt(max(nq[q] + nx[g] - 2 dot, 0)), added in f64. The dots are f32
+    matmuls in knn_topk's fixed blocks (KNN_QB zero-padded query rows
+    against KNN_CB candidates), so a query's sums do not depend on how many
+    others were asked with it; nothing of size Q x G is held. An excluded
+    pair contributes +0.0; an empty cluster's column is +0.0."""
+    Q, G, h = Xq.shape[0], X.shape[0], Xq.shape[1]
+    nq_all, nx = row_sqnorms(Xq), row_sqnorms(X)
+    onehot = torch.zeros(G, k, dtype=torch.float64)
+    onehot[torch.arange(G), labels.long()] = 1.0
+    D = torch.zeros(Q, k, dtype=torch.float64)
+    rows = torch.arange(KNN_QB)
+    for q0 in range(0, Q, KNN_QB):
+        n = min(KNN_QB, Q - q0)
+        xq = torch.zeros(KNN_QB, h, dtype=torch.float32)
+        xq[:n] = Xq[q0:q0 + n]
+        nq = torch.zeros(KNN_QB, dtype=torch.float32)
+        nq[:n] = nq_all[q0:q0 + n]
+        qi = torch.full((KNN_QB,), -1, dtype=torch.int64)
+        if q_index is not None:
+            qi[:n] = q_index[q0:q0 + n].long()
+        acc = torch.zeros(KNN_QB, k, dtype=torch.float64)
+        for lo in range(0, G, KNN_CB):
+            hi = min(G, lo + KNN_CB)
+            sc = xq @ X[lo:hi].t()
+            d2 = (nq[:, None] + nx[None, lo:hi]) - 2.0 * sc
+            d = d2.clamp_(min=0.0).sqrt_().double()
+            hit = (qi >= lo) & (qi < hi)
+            d[rows[hit], qi[hit] - lo] = 0.0
+            acc += d @ onehot[lo:hi]
+        D[q0:q0 + n] = acc[:n]
+    return D

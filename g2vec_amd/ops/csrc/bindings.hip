@@ -1013,25 +1013,32 @@ void ranksum_scores_(torch::Tensor expr, torch::Tensor labels,
 // single resident set has no tail (100 x 1M x 512: 2.13 ms at 512 blocks
 // against 3.38 ms at 2048 and 2.74 ms at 256). grid_y > 0 forces the split
 // (tests).
-int64_t knn_grid_y(int64_t Q, int64_t G, int64_t grid_y) {
-  TORCH_CHECK(Q >= 0 && G >= 0 && grid_y >= 0,
-              "knn_grid_y: negative argument");
+// op names the caller in the messages, kernel is the tile kernel whose
+// resident blocks are counted.
+template <typename K>
+int64_t tile_grid_y(const char* op, K kernel, int64_t Q, int64_t G,
+                    int64_t grid_y) {
+  TORCH_CHECK(Q >= 0 && G >= 0 && grid_y >= 0, op, ": negative argument");
   const long long nqt = (Q + KN_TILE - 1) / KN_TILE;
   const long long nct = (G + KN_TILE - 1) / KN_TILE;
   long long gy = grid_y;
   if (gy == 0) {
     int per_cu = 0;
     TORCH_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                    &per_cu, knn_tile_kernel, 256, 0) == hipSuccess &&
+                    &per_cu, kernel, 256, 0) == hipSuccess &&
                     per_cu >= 1,
-                "knn_grid_y: cannot read the kernel's occupancy");
-    const long long resident = (long long)cu_count("knn_grid_y") * per_cu;
+                op, ": cannot read the kernel's occupancy");
+    const long long resident = (long long)cu_count(op) * per_cu;
     gy = nqt > 0 ? (resident + nqt - 1) / nqt : 1;
   }
   if (gy > nct) gy = nct;
   if (gy > 65535) gy = 65535;
   if (gy < 1) gy = 1;
   return gy;
+}
+
+int64_t knn_grid_y(int64_t Q, int64_t G, int64_t grid_y) {
+  return tile_grid_y("knn_grid_y", knn_tile_kernel, Q, G, grid_y);
 }
 
 void knn_topk_(torch::Tensor Xq, torch::Tensor X,
@@ -1084,6 +1091,81 @@ void knn_topk_(torch::Tensor Xq, torch::Tensor X,
   if (gy > 1)
     launch(knn_merge_kernel, grid_for(Q, 4), 0, i32(*part_idx),
            f32(*part_val), Q, gy, k, i32(idx), f32(val));
+}
+
+// ------------------------------------------- L-group silhouettes: distance sums
+// The candidate split of cluster_dist_sums_: knn_grid_y's rule on the
+// occupancy of the instantiation that serves k.
+int64_t cds_grid_y(int64_t Q, int64_t G, int64_t k, int64_t grid_y) {
+  return k <= 4
+      ? tile_grid_y("cds_grid_y", cds_tile_kernel<4>, Q, G, grid_y)
+      : tile_grid_y("cds_grid_y", cds_tile_kernel<8>, Q, G, grid_y);
+}
+
+void cluster_dist_sums_(torch::Tensor Xq, torch::Tensor X,
+                        torch::Tensor labels,
+                        std::optional<torch::Tensor> q_index, int64_t k,
+                        int64_t grid_y, torch::Tensor nq, torch::Tensor nx,
+                        std::optional<torch::Tensor> part, torch::Tensor D) {
+  // every guard runs before the first launch: a refused call leaves nq, nx
+  // and D as they were
+  CHECK_F32(Xq); CHECK_F32(X); CHECK_I32(labels); CHECK_F32(nq); CHECK_F32(nx);
+  CHECK_F64(D);
+  check_same_device(Xq, {X, labels, nq, nx, D});
+  TORCH_CHECK(Xq.dim() == 2 && X.dim() == 2,
+              "Xq must be [Q, h] and X [G, h]");
+  const long long Q = Xq.size(0), G = X.size(0), h = X.size(1);
+  TORCH_CHECK(Xq.size(1) == h, "Xq has ", Xq.size(1), " columns, X has ", h);
+  TORCH_CHECK(h >= 4 && h % 4 == 0 && h < (1LL << 31),
+              "cluster_dist_sums: h must be a positive multiple of 4, got ", h);
+  CHECK_ROWS16(Xq); CHECK_ROWS16(X);
+  TORCH_CHECK(k >= 1 && k <= 8,
+              "cluster_dist_sums: k must be in [1, 8], got ", k);
+  TORCH_CHECK(G < (1LL << 31), "cluster_dist_sums: G must be below 2^31");
+  TORCH_CHECK(labels.dim() == 1 && labels.numel() == G,
+              "labels must be [G]");
+  if (q_index) {
+    CHECK_I32(*q_index);
+    check_same_device(Xq, {*q_index});
+    TORCH_CHECK(q_index->dim() == 1 && q_index->numel() == Q,
+                "q_index must be [Q]");
+  }
+  TORCH_CHECK(nq.dim() == 1 && nq.numel() == Q && nx.dim() == 1 &&
+                  nx.numel() == G,
+              "nq must be [Q] and nx [G]");
+  TORCH_CHECK(D.dim() == 2 && D.size(0) == Q && D.size(1) == k,
+              "D must be [Q, k]");
+  TORCH_CHECK(grid_y >= 0, "grid_y must be >= 0 (0 = automatic)");
+  check_gfx950("cluster_dist_sums");
+  const long long gy = cds_grid_y(Q, G, k, grid_y);
+  const long long nqt = (Q + KN_TILE - 1) / KN_TILE;
+  TORCH_CHECK(nqt < (1LL << 31), "cluster_dist_sums: too many queries");
+  if (gy > 1) {
+    TORCH_CHECK(part.has_value(), "cluster_dist_sums: a split over ", gy,
+                " blocks needs the partial buffer");
+    CHECK_F64(*part);
+    check_same_device(Xq, {*part});
+    TORCH_CHECK(part->numel() == Q * gy * k, "part must be [Q, ", gy, ", k]");
+  }
+  if (G > 0)
+    TORCH_CHECK(labels.min().item<int>() >= 0 && labels.max().item<int>() < k,
+                "cluster_dist_sums: labels must lie in [0, ", k, ")");
+  if (Q == 0) return;
+  if (G > 0)
+    launch(row_sqnorms_kernel, row_wave_grid(G), 0, f32(X), G, h, f32(nx));
+  launch(row_sqnorms_kernel, row_wave_grid(Q), 0, f32(Xq), Q, h, f32(nq));
+  const dim3 grid((unsigned)nqt, (unsigned)gy);
+  double* out = gy > 1 ? f64(*part) : f64(D);
+  const int* qi = q_index ? i32(*q_index) : nullptr;
+  if (k <= 4)
+    launch(cds_tile_kernel<4>, grid, 0, f32(Xq), f32(X), i32(labels), f32(nq),
+           f32(nx), qi, Q, G, h, k, out);
+  else
+    launch(cds_tile_kernel<8>, grid, 0, f32(Xq), f32(X), i32(labels), f32(nq),
+           f32(nx), qi, Q, G, h, k, out);
+  if (gy > 1)
+    launch(cds_fold_kernel, grid_for(Q * k, 256), 0, f64(*part), Q * k, gy, k,
+           f64(D));
 }
 
 // ------------------------------------------------- native host TSV parser
@@ -1250,6 +1332,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("part_idx"), py::arg("part_val"), py::arg("idx"),
         py::arg("val"),
         "k largest dots per query row, MFMA f32 + fused top-k (out-args)");
+  m.def("cds_grid_y", &cds_grid_y, py::arg("Q"), py::arg("G"), py::arg("k"),
+        py::arg("grid_y") = 0,
+        "candidate-split block count of cluster_dist_sums_");
+  m.def("cluster_dist_sums_", &cluster_dist_sums_, py::arg("Xq"), py::arg("X"),
+        py::arg("labels"), py::arg("q_index"), py::arg("k"), py::arg("grid_y"),
+        py::arg("nq"), py::arg("nx"), py::arg("part"), py::arg("D"),
+        "per-cluster sums of Euclidean distances per query row, MFMA f32 "
+        "dots + f64 sums (out-args)");
   m.def("parse_expression_tsv", &parse_expression_tsv,
         "native expression TSV parser");
 }

@@ -39,6 +39,11 @@
 //   col_moments_kernel          (step 6) f64 column sums of x and x*x for the permutation null
 //   perm_t_stats_kernel         (step 6) t^2 per (relabelling, gene) on v_mfma_f32_16x16x4_f32
 //   perm_t_counts_kernel        same body: per-gene exceed counts + per-relabelling max, no G x B output
+//   knn_tile_kernel             nearest genes: [Q,h] x [h,G] on the same MFMA, fused per-row top-k
+//   knn_merge_kernel            folds the per-block top-k lists of a candidate split
+//   row_sqnorms_kernel          f64-accumulated squared row norms, any h % 4 == 0
+//   cds_tile_kernel<KC>         silhouettes: the same product, per-cluster f64 distance sums per row
+//   cds_fold_kernel             adds the per-block sums of a candidate split in ascending order
 //
 // The templates are instantiated by their launch sites in bindings.hip, the
 // one translation unit that includes this file.
@@ -2431,5 +2436,198 @@ knn_merge_kernel(const int* __restrict__ part_idx,
       idx[q * k + lane] = li == KN_EMPTY ? -1 : li;
       val[q * k + lane] = lv;
     }
+  }
+}
+
+// ============================ L-group silhouettes: fused MFMA distance sums
+// D[q, c] = sum over the rows g of X f32[G, h] with labels[g] == c and
+// g != q_index[q] of d(q, g) = sqrtf(max(nq[q] + nx[g] - 2 dot(Xq[q], X[g]),
+// 0)), d in f32, the sums in f64. The dot is knn_tile_kernel's k-ordered
+// MFMA chain; nq / nx are the rows' squared norms (row_sqnorms_kernel).
+// Nothing of size Q x G is written, and there are no atomics: every sum is
+// added in one fixed order, so a result is bitwise equal run to run for a
+// given launch split.
+
+// out[g] = sum_j X[g, j]^2: row_norms_kernel's f64 accumulation and single
+// rounding to f32, unrooted and for any h % 4 == 0 (16-byte pieces, a lane
+// takes every 64th).
+extern "C" __global__ void __launch_bounds__(256)
+row_sqnorms_kernel(const float* __restrict__ X, long long G, int h,
+                   float* __restrict__ out) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wib = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  for (long long g = (long long)blockIdx.x * wpb + wib; g < G;
+       g += (long long)gridDim.x * wpb) {
+    const float* row = X + g * (long long)h;
+    double p = 0.0;
+    for (int j = lane * 4; j < h; j += WAVE * 4) {
+      const f32x4 x = *(const f32x4*)(row + j);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) p += (double)x[i] * (double)x[i];
+    }
+    p = wave_sum(p);
+    if (lane == 0) out[g] = (float)p;
+  }
+}
+
+// The stage, the register prefetch and the K loop are knn_tile_kernel's,
+// repeated here rather than shared (knn_tile_kernel's text and register
+// budget stay as they are; docs/KERNELS.md). The epilogue differs: once the
+// 64 x 64 dots lie in LDS, wave w reduces query rows 16w .. 16w+15 with lane
+// (fr, kk) = (lane & 15, lane >> 4) owning row 16w + fr and the candidates
+// 4i + kk, i = 0 .. 15, of the tile: KC f64 accumulators per lane, a
+// select-add of d or +0.0 per cluster. Masked entries (candidates past G,
+// which carry label -1, and a query's own index) select +0.0; padded query
+// rows are accumulated and never written. After the walk the four kk groups
+// of a row are added by a fixed xor tree.
+// out is [Q, gridDim.y, k] f64: D itself when gridDim.y == 1, else the
+// partials cds_fold_kernel adds.
+template <int KC>
+__global__ void __launch_bounds__(256)
+cds_tile_kernel(const float* __restrict__ Xq, const float* __restrict__ X,
+                const int* __restrict__ labels, const float* __restrict__ nq,
+                const float* __restrict__ nx, const int* __restrict__ q_index,
+                long long Q, long long G, int h, int k,
+                double* __restrict__ out) {
+#if defined(__gfx950__)
+  __shared__ __attribute__((aligned(16))) float lds[2 * KN_TILE * KN_LD];
+  __shared__ int lab_s[KN_TILE];
+  __shared__ float nx_s[KN_TILE];
+  float* As = lds;
+  float* Bs = lds + KN_TILE * KN_LD;
+  float* Sc = lds;                             // [64][KN_LDS] <= both tiles
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1;
+  const int fr = lane & 15, kk = lane >> 4;
+  const long long q0 = (long long)blockIdx.x * KN_TILE;
+
+  // this lane's query row: its squared norm and excluded candidate
+  const long long qrow = q0 + 16 * wid + fr;
+  const float nq_r = qrow < Q ? nq[qrow] : 0.f;
+  const long long self = (q_index && qrow < Q) ? q_index[qrow] : -1;
+
+  double acc_d[KC];
+#pragma unroll
+  for (int c = 0; c < KC; ++c) acc_d[c] = 0.0;
+
+  f32x4 ar[KN_NLD], br[KN_NLD];
+  const int srow = threadIdx.x >> 4, sc4 = (threadIdx.x & 15) * 4;
+  auto prefetch = [&](long long pc0, int pk0) {
+#pragma unroll
+    for (int i = 0; i < KN_NLD; ++i) {
+      const int row = 16 * i + srow;
+      const bool kin = pk0 + sc4 < h;
+      ar[i] = (kin && q0 + row < Q)
+          ? *(const f32x4*)(Xq + (q0 + row) * h + pk0 + sc4) : (f32x4)(0.f);
+      br[i] = (kin && pc0 + row < G)
+          ? *(const f32x4*)(X + (pc0 + row) * h + pk0 + sc4) : (f32x4)(0.f);
+    }
+  };
+
+  const long long nct = (G + KN_TILE - 1) / KN_TILE;
+  if ((long long)blockIdx.y < nct) prefetch((long long)blockIdx.y * KN_TILE, 0);
+  for (long long ct = blockIdx.y; ct < nct; ct += gridDim.y) {
+    const long long c0 = ct * KN_TILE;
+    // the tile's labels and norms, one candidate per thread of wave 0; they
+    // land in LDS with the scores
+    int lab_c = -1;
+    float nx_c = 0.f;
+    if (threadIdx.x < KN_TILE && c0 + threadIdx.x < G) {
+      lab_c = labels[c0 + threadIdx.x];
+      nx_c = nx[c0 + threadIdx.x];
+    }
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4)(0.f);
+
+    for (int k0 = 0; k0 < h; k0 += KN_KC) {
+      const int kc = (h - k0 < KN_KC) ? h - k0 : KN_KC;    // multiple of 4
+      __syncthreads();          // readers of the last chunk / score tile done
+#pragma unroll
+      for (int i = 0; i < KN_NLD; ++i) {
+        float* pa = As + (16 * i + srow) * KN_LD + sc4;    // 8-byte aligned
+        float* pb = Bs + (16 * i + srow) * KN_LD + sc4;
+        pa[0] = ar[i][0]; pa[1] = ar[i][1]; pa[2] = ar[i][2]; pa[3] = ar[i][3];
+        pb[0] = br[i][0]; pb[1] = br[i][1]; pb[2] = br[i][2]; pb[3] = br[i][3];
+      }
+      __syncthreads();
+      if (k0 + KN_KC < h)
+        prefetch(c0, k0 + KN_KC);
+      else if (ct + gridDim.y < nct)
+        prefetch((ct + gridDim.y) * KN_TILE, 0);
+      for (int kq = 0; kq < kc; kq += 4) {
+        float av[2], bv[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+          av[a] = As[(wr * 32 + a * 16 + fr) * KN_LD + kq + kk];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+          bv[b] = Bs[(wc * 32 + b * 16 + fr) * KN_LD + kq + kk];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                av[a], bv[b], acc[a][b], 0, 0, 0);
+      }
+    }
+
+    // C/D map (16x16): col = lane&15 (candidate), row = (lane>>4)*4 + reg
+    __syncthreads();                     // operand tiles dead in every wave
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+          Sc[(wr * 32 + a * 16 + kk * 4 + reg) * KN_LDS + wc * 32 + b * 16 +
+             fr] = acc[a][b][reg];
+    if (threadIdx.x < KN_TILE) {
+      lab_s[threadIdx.x] = lab_c;
+      nx_s[threadIdx.x] = nx_c;
+    }
+    __syncthreads();
+
+    const float* srow_p = Sc + (16 * wid + fr) * KN_LDS;
+#pragma unroll 4
+    for (int i = 0; i < KN_TILE / 4; ++i) {
+      const int j = 4 * i + kk;
+      const int lab = (c0 + j == self) ? -1 : lab_s[j];
+      const float d2 = nq_r + nx_s[j] - 2.f * srow_p[j];
+      const double d = (double)sqrtf(fmaxf(d2, 0.f));
+#pragma unroll
+      for (int c = 0; c < KC; ++c) acc_d[c] += (lab == c) ? d : 0.0;
+    }
+  }
+
+#pragma unroll
+  for (int c = 0; c < KC; ++c) {
+    double v = acc_d[c];
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    if (kk == 0 && qrow < Q && c < k)
+      out[(qrow * gridDim.y + blockIdx.y) * k + c] = v;
+  }
+#endif
+}
+
+// D[q, c] = the gy partials part[q, 0 .. gy-1, c] added in ascending y; one
+// thread per element of D.
+extern "C" __global__ void __launch_bounds__(256)
+cds_fold_kernel(const double* __restrict__ part, long long n, int gy, int k,
+                double* __restrict__ D) {
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long q = e / k;
+    const int c = (int)(e - q * k);
+    const double* p = part + q * gy * (long long)k + c;
+    double s = 0.0;
+    for (int y = 0; y < gy; ++y) s += p[(long long)y * k];
+    D[e] = s;
   }
 }

@@ -229,6 +229,23 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
                           info=km_info)
     if km_info:
         jsonl.emit("kmeans", backend=cfg.kmeans_backend, **km_info)
+    sil = None
+    if cfg.silhouette:
+        from .cluster_quality import silhouette
+        t0 = time.perf_counter()
+        with timers.phase("silhouette"):
+            if int((np.bincount(np.asarray(lg, dtype=np.int64),
+                                minlength=3) > 0).sum()) < 2:
+                log("    silhouette: fewer than two non-empty L-groups, "
+                    "not defined")
+            else:
+                sil = silhouette(W_dev if W_dev is not None
+                                 else torch.from_numpy(W).to(device),
+                                 lg, k=3)
+                log("    silhouette: mean %.4f (good %.4f, poor %.4f, "
+                    "other %.4f)" % ((sil["mean"],)
+                                     + tuple(sil["mean_by_cluster"])))
+        sil_seconds = time.perf_counter() - t0
 
     log(">>> 6. Select biomarkers with gene scores")
     with timers.phase("scoring"):
@@ -262,6 +279,20 @@ def run(cfg: G2VecConfig, ctx: Optional[DistContext] = None) -> Dict:
             biomarkers = scores["biomarkers"]
             if auc_all is not None:
                 scores["auc"] = auc_all
+            if cfg.silhouette:
+                scores["silhouette"] = None if sil is None else sil["s"]
+                scores["nearest_lgroup"] = (None if sil is None
+                                            else sil["nearest"])
+                if sil is not None:
+                    sel = np.asarray(scores["is_biomarker"]).astype(bool)
+                    jsonl.emit(
+                        "silhouette", mean=sil["mean"],
+                        mean_by_lgroup=[float(v) for v in
+                                        sil["mean_by_cluster"]],
+                        mean_biomarkers=(float(sil["s"][sel].mean())
+                                         if sel.any() else float("nan")),
+                        n_negative=int((sil["s"] < 0).sum()),
+                        seconds=sil_seconds)
         else:
             biomarkers = select_biomarkers(W, lg, data["expr"], data["label"],
                                            data["gene"], cfg.num_biomarker,
