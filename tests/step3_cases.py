@@ -47,7 +47,7 @@ import numpy as np
 import torch
 
 import literal_port as lp
-from g2vec_amd import ops
+from g2vec_amd import ops, pipeline
 from g2vec_amd.config import G2VecConfig
 from g2vec_amd.graph import build_group_graph, dedupe_edges
 from g2vec_amd.models.cbow import CbowTrainer
@@ -687,21 +687,14 @@ def check_trainer_helpers(device):
 # C. generate_paths: the two-stream overlap changes nothing
 # =====================================================================
 def load_study(files: dict, device):
-    """(expr_t, labels_t, edge_idx_t, n_genes) the way pipeline.run loads
-    and preprocesses a file triple."""
-    from g2vec_amd import io as gio
-    from g2vec_amd import preprocess as pp
-    data = gio.load_expression(files["expression"])
-    clinical = gio.load_clinical(files["clinical"])
-    network = gio.load_network(files["network"])
-    data["label"] = pp.match_labels(clinical, data["sample"])
-    common = pp.find_common_genes(network["gene"], data["gene"])
-    network = pp.restrict_network(network, common)
-    data = pp.restrict_data(data, common)
-    edge_idx = pp.edges_to_indices(network["edge"], common)
-    return (torch.from_numpy(data["expr"]).to(device),
-            torch.from_numpy(np.asarray(data["label"])).to(device),
-            torch.from_numpy(edge_idx).to(device), data["expr"].shape[1])
+    """(expr_t, labels_t, edge_idx_t, n_genes) as pipeline.run loads and
+    preprocesses a file triple."""
+    st = pipeline.load_study(
+        G2VecConfig(expression_file=files["expression"],
+                    clinical_file=files["clinical"],
+                    network_file=files["network"], device=str(device)),
+        log=lambda *a, **k: None)
+    return st.expr_t, st.labels_t, st.edge_idx_t, st.n_genes
 
 
 def check_generate_paths(files: dict, device, pcc_mode: str):

@@ -10,7 +10,6 @@ counts leave a wave with one row of its two-row pass) and 33000 rows: the
 grid is capped at what is resident (at most 8 blocks per CU, 2048 blocks on
 256 CUs; 256 at k*h = 8192) and a block takes 8 rows per pass, so the
 grid-stride loop runs 3 to 17 passes and the fold reads every partial."""
-import numpy as np
 import pytest
 import torch
 
@@ -18,7 +17,7 @@ import kernel_edges as ke
 import steps56_cases as sc
 from g2vec_amd import cluster, ops, scoring
 from g2vec_amd.config import G2VecConfig
-from g2vec_amd.pipeline import run
+from g2vec_amd.pipeline import load_study, run
 
 pytestmark = pytest.mark.gpu
 
@@ -258,22 +257,11 @@ def test_pipeline_with_hip_kmeans_and_device_scoring(tiny_files, tmp_path):
     assert _read(a + "_biomarkers.txt") == _read(b + "_biomarkers.txt")
 
     # same W and L-groups fed to both scoring backends: same biomarkers
-    import g2vec_amd.io as gio
-    from g2vec_amd import preprocess as pp
-    data = gio.load_expression(tiny_files["expression"])
-    clinical = gio.load_clinical(tiny_files["clinical"])
-    network = gio.load_network(tiny_files["network"])
-    data["label"] = pp.match_labels(clinical, data["sample"])
-    data = pp.restrict_data(data, pp.find_common_genes(network["gene"],
-                                                       data["gene"]))
+    st = load_study(_cfg(tiny_files, a), log=lambda *a_, **k_: None)
     W, lg = ra["W_ih"], ra["lgroups"]
-    labels = np.asarray(data["label"])
-    host = scoring.select_biomarkers(W, lg, data["expr"], labels,
-                                     data["gene"], 50)
+    host = scoring.select_biomarkers(W, lg, st.expr, st.labels, st.genes, 50)
     d_all = ops.row_norms(torch.from_numpy(W).to(DEV)).cpu().numpy()
-    t_all = ops.t_scores(torch.from_numpy(data["expr"]).to(DEV),
-                         torch.from_numpy(labels).to(DEV)).cpu().numpy()
-    dev = scoring.select_biomarkers(W, lg, data["expr"], labels,
-                                    data["gene"], 50, d_all=d_all,
-                                    t_all=t_all)
+    t_all = ops.t_scores(st.expr_t, st.labels_t).cpu().numpy()
+    dev = scoring.select_biomarkers(W, lg, st.expr, st.labels, st.genes, 50,
+                                    d_all=d_all, t_all=t_all)
     assert dev == host and dev == ra["biomarkers"]

@@ -15,13 +15,13 @@ import torch
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 
 from bench import build_dataset  # noqa: E402
-from g2vec_amd.cluster import find_lgroups  # noqa: E402
 from g2vec_amd.config import G2VecConfig  # noqa: E402
 from g2vec_amd.io import writers  # noqa: E402
 from g2vec_amd.models.cbow import CbowTrainer  # noqa: E402
 from g2vec_amd.parallel.dist import single  # noqa: E402
-from g2vec_amd.pipeline import generate_paths  # noqa: E402
-from g2vec_amd.scoring import select_biomarkers  # noqa: E402
+from g2vec_amd.pipeline import (Steps56, Study, expression_scores,  # noqa: E402
+                                generate_paths)
+from g2vec_amd.utils.obs import JsonlLogger  # noqa: E402
 
 
 def main():
@@ -47,14 +47,14 @@ def main():
     cfg = G2VecConfig(hidden=args.hidden, epochs=args.epochs, seed=0,
                       device=str(dev.type), kmeans_backend=args.kmeans,
                       scoring_backend=args.scoring)
-    expr_t = torch.from_numpy(expr).to(dev)
-    labels_t = torch.from_numpy(labels).to(dev)
-    edge_t = torch.from_numpy(edge_idx).to(dev)
+    genes = [f"G{i:07d}" for i in range(n_genes)]
+    study = Study(expr, labels, genes, edge_idx, dev)
     ctx = single(dev)
 
     t0 = time.perf_counter()
     ps, freq, n_in_paths, _stats = generate_paths(
-        cfg, expr_t, labels_t, edge_t, n_genes, ctx, log=print)
+        cfg, study.expr_t, study.labels_t, study.edge_idx_t, n_genes, ctx,
+        log=print)
     if dev.type == "cuda":
         torch.cuda.synchronize()
     t["paths"] = time.perf_counter() - t0
@@ -64,34 +64,25 @@ def main():
     res = CbowTrainer(cfg, n_genes, dev, ctx, log=lambda *a, **k: None).train(ps)
     t["train"] = time.perf_counter() - t0
 
-    W = res.W_ih.float().cpu().numpy()
-    W_dev = res.W_ih.float().to(dev).contiguous()
+    # steps 5-6 through the pipeline's own routine
+    s56 = Steps56(study, cfg, res.W_ih)
     if dev.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     km_info = {}
-    lg = find_lgroups(W_dev if cfg.kmeans_backend == "hip" else W,
-                      freq.cpu().numpy(), backend=cfg.kmeans_backend,
-                      device=dev, info=km_info)
+    lg = s56.lgroups(freq, km_info)
     t["lgroups"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
-    genes = [f"G{i:07d}" for i in range(n_genes)]
-    d_all = t_all = None
-    if cfg.scoring_backend == "device":
-        from g2vec_amd import ops
-        d_all = ops.row_norms(W_dev).cpu().numpy()
-        t_all = ops.t_scores(expr_t.float().contiguous(),
-                             labels_t).cpu().numpy()
-    bio = select_biomarkers(W, lg, expr, labels, genes, 50, d_all=d_all,
-                            t_all=t_all)
+    expr_score = expression_scores(study, cfg, print, JsonlLogger())
+    bio = s56.scores(lg, expr_score, full=False)["biomarkers"]
     t["scoring"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
     out = tempfile.mkdtemp() + "/scale"
     writers.write_biomarkers(out, bio)
     writers.write_lgroups(out, lg, genes)
-    writers.write_vectors(out, W, genes)
+    writers.write_vectors(out, s56.W, genes)
     t["write"] = time.perf_counter() - t0
 
     print({"n_genes": n_genes, "n_paths": ps.n_paths,
